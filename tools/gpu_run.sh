@@ -7,7 +7,7 @@
 # steps (outputs under gpurun_out/, named with TAG):
 #   tests[=KEXPR]    pytest -m gpu (thread timeouts, one process; -k KEXPR) -> pytest_TAG.log
 #   smoke            __graft_entry__.smoke()
-#   bench[=ARGS]     python bench.py ARGS (default: the driver's line)   -> bench_TAG.json / .err
+#   bench[=ARGS]     python bench.py ARGS (none: the headline leg; --full: every leg) -> bench_TAG.json / .err
 #   bench20          the driver's own command line (--steps 20 --warmup 5)
 #   ab=R,N,CFG;CFG   tools/ab_env.py R N CFG CFG ... (c3 decode medians) -> ab_TAG.txt
 #   diff=V,STREAM    tools/replay_diff.py STREAM with build/var/lib_V.so ("base": the product library)
@@ -55,7 +55,7 @@ for step in "$@"; do
     prof)
       (cd /tmp && export TMPDIR=/tmp &&
        timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $R/$O/prof_$TAG -o run --output-format csv -- \
-         python3 $R/bench.py --no-cpu-baseline > $R/$O/prof_$TAG.log 2>&1)
+         python3 $R/bench.py --full --no-cpu-baseline > $R/$O/prof_$TAG.log 2>&1)
       rc=$?; find $O/prof_$TAG -name "*kernel_stats*" ;;
     h265ab)
       IFS=',' read -r rounds var va vb <<< "$arg"
