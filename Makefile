@@ -14,8 +14,8 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -g -fPIC -std=c++17 $(INC) -Wno-unused-re
 HOST_SRC := $(wildcard m2dec_amd/csrc/host/*.c)
 HOST_OBJ := $(patsubst m2dec_amd/csrc/host/%.c,build/host/%.o,$(HOST_SRC))
 HIP_SRC := m2dec_amd/csrc/hip/recon_hip.hip
-HIP_HDR := m2dec_amd/csrc/hip/h265_mfma.h m2dec_amd/csrc/hip/selftest_data.h m2dec_amd/csrc/hip/recon_kernels.h m2dec_amd/csrc/hip/recon_internal.h m2dec_amd/csrc/host/h265_dec.h
-HIP_OBJ := build/hip/recon_hip.o build/hip/runtime.o build/hip/m2v_hip.o build/hip/h265_hip.o
+HIP_HDR := m2dec_amd/csrc/hip/h265_mfma.h m2dec_amd/csrc/hip/selftest_data.h m2dec_amd/csrc/hip/recon_kernels.h m2dec_amd/csrc/hip/recon_internal.h m2dec_amd/csrc/host/h265_dec.h m2dec_amd/csrc/host/frame_out.h
+HIP_OBJ := build/hip/recon_hip.o build/hip/runtime.o build/hip/m2v_hip.o build/hip/h265_hip.o build/hip/frame_out.o
 
 LIB := m2dec_amd/lib/libm2dec_amd.so
 ORACLE := oracle/_build/liboracle.so
@@ -77,27 +77,27 @@ $(M2VGEN): tools/m2vgen/m2vgen.c m2dec_amd/csrc/host/mpeg2_tables.c m2dec_amd/cs
 	$(CC) -O2 -g -Wall -std=gnu11 $(INC) -o $@ tools/m2vgen/m2vgen.c m2dec_amd/csrc/host/mpeg2_tables.c -lm
 
 DBG_LIB := build/dbg/libm2dec_amd_stamps.so
-$(DBG_LIB): $(HOST_OBJ) $(HIP_SRC) $(HIP_HDR) build/hip/runtime.o build/hip/m2v_hip.o build/hip/h265_hip.o
+$(DBG_LIB): $(HOST_OBJ) $(HIP_SRC) $(HIP_HDR) build/hip/runtime.o build/hip/frame_out.o build/hip/m2v_hip.o build/hip/h265_hip.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -DM2DEC_STAMPS -c $(HIP_SRC) -o build/dbg/recon_hip_stamps.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HOST_OBJ) build/dbg/recon_hip_stamps.o build/hip/runtime.o build/hip/m2v_hip.o build/hip/h265_hip.o -Wl,--no-undefined
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HOST_OBJ) build/dbg/recon_hip_stamps.o build/hip/runtime.o build/hip/frame_out.o build/hip/m2v_hip.o build/hip/h265_hip.o -Wl,--no-undefined
 
 stamps: $(DBG_LIB)
 
 # H.265 CTU kernel stamps (tools/stamps_h265.py)
 H5S_LIB := build/h5s/libm2dec_amd_h5stamps.so
-$(H5S_LIB): $(HOST_OBJ) m2dec_amd/csrc/hip/h265_hip.hip $(HIP_HDR) build/hip/recon_hip.o build/hip/runtime.o build/hip/m2v_hip.o
+$(H5S_LIB): $(HOST_OBJ) m2dec_amd/csrc/hip/h265_hip.hip $(HIP_HDR) build/hip/recon_hip.o build/hip/runtime.o build/hip/frame_out.o build/hip/m2v_hip.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -DH265_STAMPS -c m2dec_amd/csrc/hip/h265_hip.hip -o build/h5s/h265_hip_stamps.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HOST_OBJ) build/hip/recon_hip.o build/hip/runtime.o build/hip/m2v_hip.o build/h5s/h265_hip_stamps.o -Wl,--no-undefined
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HOST_OBJ) build/hip/recon_hip.o build/hip/runtime.o build/hip/frame_out.o build/hip/m2v_hip.o build/h5s/h265_hip_stamps.o -Wl,--no-undefined
 
 h5stamps: $(H5S_LIB)
 
 # diagnostic variants: make variant V=NAME FLAGS="-DX"
-variant: $(HOST_OBJ) build/hip/runtime.o build/hip/m2v_hip.o build/hip/h265_hip.o
+variant: $(HOST_OBJ) build/hip/runtime.o build/hip/frame_out.o build/hip/m2v_hip.o build/hip/h265_hip.o
 	@mkdir -p build/var
 	$(HIPCC) $(HIPFLAGS) $(FLAGS) -c $(HIP_SRC) -o build/var/recon_$(V).o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/var/lib_$(V).so $(HOST_OBJ) build/var/recon_$(V).o build/hip/runtime.o build/hip/m2v_hip.o build/hip/h265_hip.o -Wl,--no-undefined
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/var/lib_$(V).so $(HOST_OBJ) build/var/recon_$(V).o build/hip/runtime.o build/hip/frame_out.o build/hip/m2v_hip.o build/hip/h265_hip.o -Wl,--no-undefined
 
 clean:
 	rm -rf build m2dec_amd/lib oracle/_build tools/_build
@@ -106,18 +106,18 @@ clean:
 
 # inter MB phase stamps (tools/stamps_interw.py)
 STW_LIB := build/dbg/libm2dec_amd_stampw.so
-$(STW_LIB): $(HOST_OBJ) $(HIP_SRC) $(HIP_HDR) build/hip/runtime.o build/hip/m2v_hip.o build/hip/h265_hip.o
+$(STW_LIB): $(HOST_OBJ) $(HIP_SRC) $(HIP_HDR) build/hip/runtime.o build/hip/frame_out.o build/hip/m2v_hip.o build/hip/h265_hip.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -DM2DEC_STAMPS -DM2DEC_STAMPW -DM2DEC_NO_STAMPI -c $(HIP_SRC) -o build/dbg/recon_hip_stampw.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HOST_OBJ) build/dbg/recon_hip_stampw.o build/hip/runtime.o build/hip/m2v_hip.o build/hip/h265_hip.o -Wl,--no-undefined
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HOST_OBJ) build/dbg/recon_hip_stampw.o build/hip/runtime.o build/hip/frame_out.o build/hip/m2v_hip.o build/hip/h265_hip.o -Wl,--no-undefined
 
 stampw: $(STW_LIB)
 
 # deblocking filter sub-step stamps (tools/stamps_dbk.py)
 STD_LIB := build/dbg/libm2dec_amd_stampd.so
-$(STD_LIB): $(HOST_OBJ) $(HIP_SRC) $(HIP_HDR) build/hip/runtime.o build/hip/m2v_hip.o build/hip/h265_hip.o
+$(STD_LIB): $(HOST_OBJ) $(HIP_SRC) $(HIP_HDR) build/hip/runtime.o build/hip/frame_out.o build/hip/m2v_hip.o build/hip/h265_hip.o
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -DM2DEC_STAMPS -DM2DEC_STAMPD -DM2DEC_NO_STAMPI -c $(HIP_SRC) -o build/dbg/recon_hip_stampd.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HOST_OBJ) build/dbg/recon_hip_stampd.o build/hip/runtime.o build/hip/m2v_hip.o build/hip/h265_hip.o -Wl,--no-undefined
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(HOST_OBJ) build/dbg/recon_hip_stampd.o build/hip/runtime.o build/hip/frame_out.o build/hip/m2v_hip.o build/hip/h265_hip.o -Wl,--no-undefined
 
 stampd: $(STD_LIB)

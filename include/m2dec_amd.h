@@ -104,8 +104,68 @@ int m2dec_amd_decode_stream2(const uint8_t *data, size_t len, const m2r_backend_
                              void (*on_frame)(void *arg, const m2d_frame_t *f), void *arg,
                              m2dec_amd_stats_t *stats);
 
+/* ---- device-resident output: frames delivered cropped into device memory the caller names, as
+ * NV12, interleaved RGB or planar RGB, without a host round trip.  The conversion is integer arithmetic, stated
+ * once (host: frame_out.c, gfx950: frame_out.hip k_frame_out, bit-identical): for output pixel (x, y), with
+ * (sx, sy) = (x + crop_left, y + crop_top), Y = luma[sy][sx], (Cb, Cr) = chroma[sy >> 1][(sx >> 1) * 2 + {0, 1}]
+ * (nearest neighbour), C = Y - yo, D = Cb - 128, E = Cr - 128:
+ *   R = clip255((ky C + rv E + 128) >> 8), G = clip255((ky C + gu D + gv E + 128) >> 8), B = clip255((ky C + bu D + 128) >> 8)
+ * (ky, yo, rv, gu, gv, bu) = BT.601 limited (298, 16, 409, -100, -208, 516), BT.709 limited (298, 16, 459, -55,
+ * -136, 541), BT.601 full (256, 0, 359, -88, -183, 454), BT.709 full (256, 0, 403, -48, -120, 475).
+ * NV12: the cropped Y rows, then the cropped CbCr rows, no pitch (the bytes FileWriterMd5 hashes);
+ * RGB: H x W x 3 interleaved; RGBP: 3 x H x W planar.  Crops and the cropped size must be even (-1 otherwise). */
+enum { M2DEC_AMD_OUT_NV12 = 0, M2DEC_AMD_OUT_RGB = 1, M2DEC_AMD_OUT_RGBP = 2 };
+enum { M2DEC_AMD_BT709 = 0, M2DEC_AMD_BT601 = 1 };
+typedef struct {
+	size_t size;          /* sizeof of the caller's struct */
+	int format, matrix, full_range;
+	/* called on the thread that called the driver, once per output frame in output order, before the frame is
+	 * written: the device address (on `device`) for frame `index` of width x height (cropped), `bytes` long;
+	 * NULL ends the decode with an error */
+	void *(*frame_dst)(void *arg, int index, int width, int height, size_t bytes);
+	void *arg;
+} m2dec_amd_devout_t;
+/* bytes of one cropped width x height frame in `format` (0 for a bad format or an odd / non-positive size) */
+size_t m2dec_amd_frame_out_bytes(int format, int width, int height);
+/* The conversion over a host frame into out (m2dec_amd_frame_out_bytes long); only size, format, matrix and
+ * full_range of cfg are read.  0, or -1 (nothing written) for a bad cfg, an odd crop or an empty cropped frame. */
+int m2dec_amd_frame_convert_host(const m2d_frame_t *f, const m2dec_amd_devout_t *cfg, uint8_t *out);
+/* Kernel parity entry: the host planes (luma width x height, stride width; chroma width x height / 2) are uploaded
+ * in the back end's picture layout, k_frame_out writes the cropped frame to (device buffer) + out_offset
+ * (0 .. 15: unaligned destinations), and the device buffer's bytes [out_offset - guard, out_offset + bytes + guard)
+ * with guard = 64 come back into out_host (bytes + 128 long; the guards hold 0xA5 when nothing wrote them). */
+int m2dec_amd_hip_frame_convert(int device, const uint8_t *luma, const uint8_t *chroma, int width, int height,
+                                const int16_t crop[4], const m2dec_amd_devout_t *cfg, uint8_t *out_host,
+                                size_t out_offset);
+/* The H.264 stream driver (the loop and output order of m2dec_amd_decode_stream2, `h264dec -d dpb`) with every
+ * output frame converted on the device into out->frame_dst's address: no pixel crosses to the host
+ * (stats->d2h_bytes and host_copy_us stay 0).  On return every frame is complete and visible to any stream of
+ * the process.  Returns the number of frames, or -1. */
+int m2dec_amd_decode_stream_device(const uint8_t *data, size_t len, int device, int dpb,
+                                   const m2dec_amd_devout_t *out, m2dec_amd_stats_t *stats);
+/* device memory for callers without a HIP runtime of their own (Python): allocate / free on `device`, and a
+ * synchronous device -> host read (0 / -1) */
+void *m2dec_amd_device_alloc(int device, size_t bytes);
+void m2dec_amd_device_free(int device, void *p);
+int m2dec_amd_device_read(int device, const void *src_dev, void *dst_host, size_t bytes);
+
 /* HIP back end constructor (m2dec_amd/csrc/hip/recon_hip.hip). */
 int m2dec_amd_hip_backend_create(m2r_backend_t *out, int device);
+/* Device-output mode of a HIP back end (set before its first set_frames; 0 / -1): the per-slot staging buffers
+ * are device memory holding the raw NV12 picture, sync_frame neither waits for pixels nor writes the caller's
+ * frames (which may then be small placeholders), and the caller takes each frame with emit:
+ *   emit(be, slot, crop, cfg, dst_dev): k_frame_out from the slot's staging to dst_dev, enqueued behind the
+ *     picture's copy; call it after the frame left get / peek_decoded_frame and before the next decode_picture
+ *     (the lifetime get_decoded_frame gives a host frame).  The staging is not reused before the conversion read it.
+ *   finish(be): waits for everything emitted (then visible to every stream of the process) and checks the
+ *     kernels' error word (-1: a wavefront hand-off failed); call it before the frames are used and before destroy.
+ *   frame_out_timing (process-wide): HIP-event time of the k_frame_out launches of finished back ends' emits and
+ *     their count since the last reset (M2DEC_AMD_TIMING=0: not timed). */
+int m2dec_amd_hip_backend_set_device_output(const m2r_backend_t *be, int on);
+int m2dec_amd_hip_backend_emit(const m2r_backend_t *be, int slot, const int16_t crop[4], const m2dec_amd_devout_t *cfg,
+                               void *dst_dev);
+int m2dec_amd_hip_backend_finish(const m2r_backend_t *be);
+int m2dec_amd_frame_out_timing(double *kernel_us, int64_t *frames, int reset);
 /* Non-zero if a gfx950 device is usable by this process. */
 int m2dec_amd_hip_available(void);
 /* page-lock host memory for the life of the process (or until unpin); HIP back ends then skip

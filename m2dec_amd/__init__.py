@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("M2DEC_AMD_LIB") or os.path.join(_HERE, "lib", "libm2d
 
 __all__ = [
     "LIB_PATH", "Frame", "Backend", "Stats", "HipTiming", "lib", "hip_available", "HipBackend",
-    "decode_stream", "decode_stream_md5", "decode_streams", "decode_m2v", "m2v_last_checks", "decode_table_frames", "frame_md5", "frame_nv12", "H264Decoder", "Trace", "HipReplay", "TracePic",
+    "decode_stream", "decode_stream_md5", "decode_streams", "decode_m2v", "m2v_last_checks", "decode_table_frames", "frame_md5", "frame_nv12", "DevOut", "DeviceFrames", "decode_to_device", "frame_convert_host", "hip_frame_convert", "frame_out_timing", "H264Decoder", "Trace", "HipReplay", "TracePic",
 ]
 
 
@@ -91,6 +91,17 @@ class TracePic(ctypes.Structure):
 
 
 ON_FRAME = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.POINTER(Frame))
+FRAME_DST = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t)
+
+
+class DevOut(ctypes.Structure):
+    """m2dec_amd_devout_t (include/m2dec_amd.h): output format, matrix, range and the destination callback."""
+    _fields_ = [("size", ctypes.c_size_t), ("format", ctypes.c_int), ("matrix", ctypes.c_int),
+                ("full_range", ctypes.c_int), ("frame_dst", FRAME_DST), ("arg", ctypes.c_void_p)]
+
+
+OUT_FORMATS = {"nv12": 0, "rgb": 1, "rgbp": 2}
+OUT_MATRICES = {"bt709": 0, "bt601": 1}
 
 _lib = None
 
@@ -186,6 +197,26 @@ def lib() -> ctypes.CDLL:
                                              ctypes.POINTER(ctypes.c_int16)]
         L.m2dec_amd_hip_replay_destroy.argtypes = [vp]
         L.m2dec_amd_hip_replay_destroy.restype = None
+        L.m2dec_amd_frame_out_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        L.m2dec_amd_frame_out_bytes.restype = ctypes.c_size_t
+        L.m2dec_amd_frame_convert_host.argtypes = [ctypes.POINTER(Frame), ctypes.POINTER(DevOut), vp]
+        L.m2dec_amd_frame_convert_host.restype = ctypes.c_int
+        L.m2dec_amd_hip_frame_convert.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.POINTER(ctypes.c_int16), ctypes.POINTER(DevOut), vp,
+                                                  ctypes.c_size_t]
+        L.m2dec_amd_hip_frame_convert.restype = ctypes.c_int
+        L.m2dec_amd_decode_stream_device.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.POINTER(DevOut), ctypes.POINTER(Stats)]
+        L.m2dec_amd_decode_stream_device.restype = ctypes.c_int
+        L.m2dec_amd_device_alloc.argtypes = [ctypes.c_int, ctypes.c_size_t]
+        L.m2dec_amd_device_alloc.restype = vp
+        L.m2dec_amd_device_free.argtypes = [ctypes.c_int, vp]
+        L.m2dec_amd_device_free.restype = None
+        L.m2dec_amd_device_read.argtypes = [ctypes.c_int, vp, vp, ctypes.c_size_t]
+        L.m2dec_amd_device_read.restype = ctypes.c_int
+        L.m2dec_amd_frame_out_timing.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
+                                                 ctypes.c_int]
+        L.m2dec_amd_frame_out_timing.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -319,6 +350,136 @@ def decode_stream_md5(data: bytes, device: int = 0, dpb: int = -1, stats: Option
         raise RuntimeError(f"m2dec_amd: decode failed (last_error={st.last_error}, frames={st.frames_out})")
     raw = buf.raw
     return [raw[35 * i:35 * i + 32].decode() for i in range(min(n, cap))]
+
+
+def _devout(fmt: str, matrix: str, full_range: bool) -> DevOut:
+    if fmt not in OUT_FORMATS or matrix not in OUT_MATRICES:
+        raise ValueError(f"m2dec_amd: format {fmt!r} (nv12 / rgb / rgbp) or matrix {matrix!r} (bt709 / bt601) unknown")
+    return DevOut(size=ctypes.sizeof(DevOut), format=OUT_FORMATS[fmt], matrix=OUT_MATRICES[matrix],
+                  full_range=1 if full_range else 0)
+
+
+def frame_convert_host(f: Frame, fmt: str = "rgb", matrix: str = "bt709", full_range: bool = False) -> bytes:
+    """The output conversion (include/m2dec_amd.h) of a host frame on the CPU (m2dec_amd_frame_convert_host): the
+    cropped frame as NV12, interleaved RGB or planar RGB bytes.  Raises ValueError for an odd crop or size."""
+    L = lib()
+    cfg = _devout(fmt, matrix, full_range)
+    n = L.m2dec_amd_frame_out_bytes(cfg.format, f.width - f.crop[0] - f.crop[1], f.height - f.crop[2] - f.crop[3])
+    out = ctypes.create_string_buffer(max(1, n))
+    if not n or L.m2dec_amd_frame_convert_host(ctypes.byref(f), ctypes.byref(cfg), out) < 0:
+        raise ValueError("m2dec_amd: frame_convert_host refused the frame (odd or empty crop)")
+    return out.raw[:n]
+
+
+def hip_frame_convert(luma: bytes, chroma: bytes, width: int, height: int, crop=(0, 0, 0, 0), fmt: str = "rgb",
+                      matrix: str = "bt709", full_range: bool = False, device: int = 0, out_offset: int = 0):
+    """Kernel parity entry (m2dec_amd_hip_frame_convert): k_frame_out over the uploaded planes, written
+    ``out_offset`` bytes into a device buffer.  Returns (frame bytes, the 64 guard bytes before, the 64 after)."""
+    L = lib()
+    cfg = _devout(fmt, matrix, full_range)
+    n = L.m2dec_amd_frame_out_bytes(cfg.format, width - crop[0] - crop[1], height - crop[2] - crop[3])
+    out = ctypes.create_string_buffer(n + 128)
+    cr = (ctypes.c_int16 * 4)(*crop)
+    if len(luma) < width * height or len(chroma) < width * height // 2:
+        raise ValueError("m2dec_amd: hip_frame_convert: planes shorter than width x height")
+    if L.m2dec_amd_hip_frame_convert(device, luma, chroma, width, height, cr, ctypes.byref(cfg), out, out_offset) < 0:
+        raise RuntimeError("m2dec_amd: hip_frame_convert failed (odd crop, bad geometry or no gfx950 device)")
+    raw = out.raw
+    return raw[64:64 + n], raw[:64], raw[64 + n:]
+
+
+def frame_out_timing(reset: bool = False):
+    """(HIP-event microseconds, launches) of k_frame_out over the device decodes finished so far."""
+    us, n = ctypes.c_double(), ctypes.c_int64()
+    lib().m2dec_amd_frame_out_timing(ctypes.byref(us), ctypes.byref(n), 1 if reset else 0)
+    return us.value, n.value
+
+
+class DeviceFrames:
+    """The output frames of ``decode_to_device`` in device memory: ``n`` frames of ``shape[1:]`` bytes each, packed,
+    on ``device``.  ``numpy()`` copies them to the host; ``__cuda_array_interface__`` (version 3) hands the memory to
+    torch or cupy without a copy (``torch.as_tensor(frames, device="cuda:0")``) — the memory lives until ``close()``."""
+
+    def __init__(self, device: int, fmt: str):
+        self.device = device
+        self.fmt = fmt
+        self.ptr = None
+        self.capacity = 0
+        self.n = 0
+        self.width = self.height = 0
+        self.frame_bytes = 0
+
+    @property
+    def shape(self):
+        w, h = self.width, self.height
+        return {"rgb": (self.n, h, w, 3), "rgbp": (self.n, 3, h, w), "nv12": (self.n, h * 3 // 2, w)}[self.fmt]
+
+    @property
+    def __cuda_array_interface__(self):
+        if not self.ptr:
+            raise RuntimeError("m2dec_amd: DeviceFrames is empty or closed")
+        return {"shape": self.shape, "typestr": "|u1", "data": (int(self.ptr), False), "version": 3, "strides": None,
+                "stream": None}
+
+    def numpy(self):
+        import numpy as np
+        out = np.empty(self.shape, dtype=np.uint8)
+        if out.size and lib().m2dec_amd_device_read(self.device, self.ptr, out.ctypes.data, out.size) < 0:
+            raise RuntimeError("m2dec_amd: device read failed")
+        return out
+
+    def close(self) -> None:
+        if self.ptr:
+            lib().m2dec_amd_device_free(self.device, self.ptr)
+        self.ptr = None
+        self.n = 0
+
+    def __len__(self):
+        return self.n
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+
+def decode_to_device(data: bytes, device: int = 0, fmt: str = "rgb", matrix: str = "bt709", full_range: bool = False,
+                     dpb: int = -1, stats: Optional[Stats] = None) -> DeviceFrames:
+    """Decode an H.264 stream with the HIP back end and leave every output frame, cropped, in device memory
+    (m2dec_amd_decode_stream_device): ``fmt`` "rgb" (N, H, W, 3), "rgbp" (N, 3, H, W) or "nv12" (N, H * 3 / 2, W),
+    converted by k_frame_out with ``matrix`` "bt709" / "bt601" in limited or full range.  No pixel crosses to the
+    host (``stats.d2h_bytes`` stays 0).  One geometry per stream: a frame of another size ends the decode."""
+    L = lib()
+    if not L.m2dec_amd_hip_available():
+        raise RuntimeError("m2dec_amd: no usable gfx950 device for the HIP back end")
+    cfg = _devout(fmt, matrix, full_range)
+    fr = DeviceFrames(device, fmt)
+    cap = _max_frames(data)
+
+    def _dst(_arg, index, width, height, nbytes):
+        if fr.ptr is None:  # the first frame: the geometry is known now
+            fr.ptr = L.m2dec_amd_device_alloc(device, nbytes * cap)
+            fr.capacity, fr.width, fr.height, fr.frame_bytes = cap, width, height, nbytes
+        if not fr.ptr or index >= fr.capacity or (width, height, nbytes) != (fr.width, fr.height, fr.frame_bytes):
+            return None
+        fr.n = index + 1
+        return fr.ptr + index * nbytes
+
+    cfg.frame_dst = FRAME_DST(_dst)
+    st = stats if stats is not None else Stats()
+    n = L.m2dec_amd_decode_stream_device(data, len(data), device, dpb, ctypes.byref(cfg), ctypes.byref(st))
+    if n < 0:
+        fr.close()
+        raise RuntimeError(f"m2dec_amd: device decode failed (last_error={st.last_error}, frames={st.frames_out})")
+    fr.n = n
+    return fr
 
 
 def decode_stream_md5_backend(data: bytes, backend: Backend, parse_threads: int = 4, md5_threads: int = 2,

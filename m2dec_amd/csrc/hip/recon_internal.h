@@ -7,6 +7,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "m2d_recon.h"
+#include "m2dec_amd.h"
 
 #define HBI_BYTES 48 /* I-picture intra hand-off per MB: bottom luma row (16 B) + bottom chroma row (16 B) in six
                         * u64 words of 6 bytes + a 16-bit picture tag each */
@@ -99,6 +100,12 @@ static inline int picture_blocks_dp(int inter_workers, int row_wgs, int Hmb, boo
 	const int pairs = (Hmb + 1) / 2;
 	return has_inter ? inter_workers + (row_wgs < pairs ? row_wgs : pairs) : pairs;
 }
+
+/* frame_out.hip: enqueue k_frame_out on stream s — the picture at `pic` (the back end's layout: NV12, luma stride W,
+ * chroma at + W * H; 4-byte aligned) cropped and converted as cfg says into dst (device memory, any alignment,
+ * m2dec_amd_frame_out_bytes long).  -1 without a launch for a bad cfg, an odd crop or an empty cropped frame. */
+int m2r_frame_out_launch(hipStream_t s, const uint8_t *pic, int W, int H, const int16_t crop[4],
+                         const m2dec_amd_devout_t *cfg, uint8_t *dst);
 
 /* dynamic LDS bytes of one k_deblock workgroup for a W-sample-wide picture */
 size_t m2r_deblock_lds_bytes(int W, int Wmb);

@@ -386,6 +386,7 @@ struct DevPool {
 	};
 	std::vector<Block> blocks; /* oldest given first */
 	size_t kept = 0;
+	size_t cap = kPoolDevBytes;
 
 	hipError_t take(int dev, void **p, size_t n)
 	{
@@ -409,8 +410,8 @@ struct DevPool {
 		std::vector<void *> drop;
 		{
 			std::lock_guard<std::mutex> lk(mu);
-			if (n <= kPoolDevBytes) {
-				while (!blocks.empty() && kept + n > kPoolDevBytes) {
+			if (n <= cap) {
+				while (!blocks.empty() && kept + n > cap) {
 					drop.push_back(blocks.front().p);
 					kept -= blocks.front().n;
 					blocks.erase(blocks.begin());
@@ -423,7 +424,8 @@ struct DevPool {
 		for (void *q : drop) (void)hipFree(q);
 		if (p) (void)hipFree(p);
 	}
-} g_dev;
+};
+DevPool g_dev;
 
 /* Host ranges page-locked for the life of the process (m2dec_amd_hip_pin: the stream driver's pooled
  * frame memory).  set_frames does not register frames inside them again — a new stream reuses the
@@ -1159,6 +1161,19 @@ struct StagePool {
  * points into caller memory. */
 const size_t kStgTail = 64;
 
+/* Device-output mode (m2dec_amd_hip_backend_set_device_output): the caller takes the frames on the device
+ * (k_frame_out, frame_out.hip), so the staging buffers are device memory holding the raw NV12 picture, pooled per
+ * process like the pinned ones (exact size, at most 1 GiB kept): once a stream's buffers exist the decode path
+ * neither allocates nor frees.  Staging is kept, not skipped: a picture buffer is rewritten by the next picture
+ * decoded into it, long before an output frame's lifetime (until the caller's next decode_picture) ends. */
+struct DStagePool : DevPool {
+	DStagePool() { cap = (size_t)1 << 30; }
+} g_dstage;
+/* k_frame_out launches of destroyed device-output back ends (m2dec_amd_frame_out_timing) */
+std::mutex g_fo_mu;
+double g_fo_us = 0;
+int64_t g_fo_frames = 0;
+
 /* up to 3 ranges per picture x BMAX pictures, copied by k_upload (blockIdx.y = range) */
 struct UploadList {
 	const uint8_t *src[3 * 4];
@@ -1260,6 +1275,17 @@ struct HipBackend {
 	bool kcopy = true; /* records up by k_upload (M2DEC_AMD_KCOPY) */
 	int kd2h = 2;      /* frames down: 0 SDMA, 1 k_upload, 2 k_upload while several back ends live (M2DEC_AMD_KCOPY_D2H) */
 	bool prestage = true; /* decode ahead: copy-out right behind the kernel (M2DEC_AMD_PRESTAGE) */
+	/* device-output mode: stg[] are device buffers (g_dstage), sync_frame copies nothing, the caller emits each
+	 * frame from its slot's staging (m2dec_amd_hip_backend_emit) */
+	bool devout = false;
+	hipEvent_t emit_ev[64] = {};   /* the conversion reading stg[slot] is complete (recorded on the copy stream) */
+	bool emit_pending[64] = {};    /* ... and has to be waited for before stg[slot] is overwritten or pooled */
+	hipEvent_t fo_ev[64][2] = {};  /* timing: around slot's k_frame_out */
+	bool fo_timed[64] = {};
+	double fo_us = 0;
+	int64_t fo_frames = 0;
+	std::mutex fo_mu;              /* fo_timed / fo_us / fo_frames: emit (API thread) and stage_drop (a pool worker) */
+	int *err_host = nullptr;       /* pinned: the kernels' error word as of finish */
 	/* guards Arena::held / pending / ext: records_busy reads them from any thread while the decoder's
 	 * serial calls (acquire, submit, flush, bind) change them */
 	std::mutex arena_mu;
@@ -1296,11 +1322,34 @@ void flush_timing(HipBackend *b, TimingSlot &t)
 	t.pending = false;
 }
 
+/* device-output mode: slot's finished k_frame_out into the back end's timing (its second event has fired) */
+void fo_collect(HipBackend *b, int slot)
+{
+	float ms;
+	std::lock_guard<std::mutex> lk(b->fo_mu);
+	if (!b->fo_timed[slot]) return;
+	b->fo_timed[slot] = false;
+	if (hipEventElapsedTime(&ms, b->fo_ev[slot][0], b->fo_ev[slot][1]) != hipSuccess) return;
+	b->fo_us += ms * 1e3;
+	b->fo_frames++;
+}
+
 /* slot i's staging buffer goes back to the pool (its copy, if any, is complete) */
 void stage_drop(HipBackend *b, int i)
 {
 	if (i >= 64 && b->stg[i]) b->prestaged--;
-	g_stage.give(b->stg[i], b->stg_size + kStgTail);
+	if (b->devout) {
+		/* device staging: nothing waited for its copy in sync_frame, and a conversion may still read it */
+		if (b->stg[i] && b->slot_pending[i]) (void)hipEventSynchronize(b->slot_ev[i]);
+		if (i < 64 && b->emit_pending[i]) {
+			(void)hipEventSynchronize(b->emit_ev[i]);
+			fo_collect(b, i);
+			b->emit_pending[i] = false;
+		}
+		g_dstage.give(b->sc.dev, b->stg[i], b->stg_size + kStgTail);
+	} else {
+		g_stage.give(b->stg[i], b->stg_size + kStgTail);
+	}
 	b->stg[i] = nullptr;
 	b->slot_pending[i] = false;
 }
@@ -1340,6 +1389,29 @@ int be_set_frames(void *self, int n, const m2d_frame_t *frames, int width, int h
 /* enqueue the copy of picture buffer `cur` into slot's staging buffer on stream s (after what s waits for) */
 int stage_copy(HipBackend *b, const uint8_t *cur, int slot, hipStream_t s)
 {
+	if (b->devout) {
+		/* device to device, by k_upload; a buffer the slot kept (sync_frame drops nothing in this mode) is
+		 * overwritten only behind its last copy and the conversion that read it */
+		if (b->stg[slot]) {
+			if (b->slot_pending[slot]) CHECK(hipStreamWaitEvent(s, b->slot_ev[slot], 0));
+			if (slot < 64 && b->emit_pending[slot]) {
+				CHECK(hipStreamWaitEvent(s, b->emit_ev[slot], 0));
+				b->emit_pending[slot] = false;
+			}
+		} else if (g_dstage.take(b->sc.dev, (void **)&b->stg[slot], b->stg_size + kStgTail) != hipSuccess) {
+			b->stg[slot] = nullptr;
+			fprintf(stderr, "m2dec_amd: no device staging memory\n");
+			return -1;
+		}
+		UploadList ul;
+		ul.n = 0;
+		ul.add(cur, b->stg[slot], b->stg_size);
+		hipLaunchKernelGGL(k_upload, dim3(256, 1), dim3(256), 0, s, ul);
+		CHECK(hipGetLastError());
+		CHECK(hipEventRecord(b->slot_ev[slot], s));
+		b->slot_pending[slot] = true;
+		return 0;
+	}
 	if (!b->stg[slot] && !(b->stg[slot] = g_stage.take(b->stg_size + kStgTail))) {
 		fprintf(stderr, "m2dec_amd: no pinned staging memory\n");
 		return -1;
@@ -1646,6 +1718,9 @@ int be_sync(void *self, int slot)
 {
 	HipBackend *b = (HipBackend *)self;
 	if (slot < 0 || slot >= 64) return -1;
+	/* device-output mode: no pixel goes to the caller's frame and nothing is waited for; the slot keeps its
+	 * staging for m2dec_amd_hip_backend_emit, and the error word is read in m2dec_amd_hip_backend_finish */
+	if (b->devout) return 0;
 	/* (no flush here: sync_frame runs on the API thread while a pool worker may be inside submit / bind /
 	 * flush — those three, acquire and set_frames are the serial back-end calls.  The slot's picture was
 	 * launched when it was bound, or when it was submitted without decode ahead.) */
@@ -1688,7 +1763,7 @@ int be_sync(void *self, int slot)
 int be_ready(void *self, int slot)
 {
 	HipBackend *b = (HipBackend *)self;
-	if (slot < 0 || slot >= 64 || !b->slot_pending[slot]) return 1;
+	if (slot < 0 || slot >= 64 || !b->slot_pending[slot] || b->devout) return 1;
 	return hipEventQuery(b->slot_ev[slot]) == hipSuccess;
 }
 
@@ -1737,6 +1812,18 @@ void be_destroy(void *self)
 	g_pool.put_stream(b->sc.dev, b->copy); /* (synchronises it: every staging copy is complete) */
 	b->copy = nullptr;
 	for (int i = 0; i < 128; ++i) stage_drop(b, i);
+	if (b->devout) {
+		for (int i = 0; i < 64; ++i) {
+			fo_collect(b, i); /* (the copy stream is idle: every conversion finished) */
+			g_pool.put_event(b->sc.dev, false, b->emit_ev[i]);
+			g_pool.put_event(b->sc.dev, true, b->fo_ev[i][0]);
+			g_pool.put_event(b->sc.dev, true, b->fo_ev[i][1]);
+		}
+		if (b->err_host) (void)hipHostFree(b->err_host);
+		std::lock_guard<std::mutex> lk(g_fo_mu);
+		g_fo_us += b->fo_us;
+		g_fo_frames += b->fo_frames;
+	}
 	for (auto &a : b->ar) {
 		g_arenas.give(b->sc.dev, a); /* (every kernel reading it finished: sync_all above) */
 		g_pool.put_event(b->sc.dev, false, a.consumed);
@@ -1850,6 +1937,85 @@ extern "C" int m2dec_amd_hip_backend_budget(const m2r_backend_t *be, m2dec_amd_h
 	return 0;
 }
 
+/* ---- device-output mode (include/m2dec_amd.h) */
+static HipBackend *hip_backend_of(const m2r_backend_t *be)
+{
+	return be && be->self && be->sync_frame == be_sync ? (HipBackend *)be->self : nullptr; /* (not another back end) */
+}
+
+extern "C" int m2dec_amd_hip_backend_set_device_output(const m2r_backend_t *be, int on)
+{
+	HipBackend *b = hip_backend_of(be);
+	if (!b || b->nframes) return -1; /* before the first set_frames: no pinned staging exists yet */
+	if (!on) return b->devout ? -1 : 0;
+	if (b->devout) return 0;
+	CHECK(hipSetDevice(b->sc.dev));
+	/* everything emit uses exists before the pipeline's threads do (emit runs beside their bind / submit) */
+	if (!b->copy) CHECK(g_pool.stream(b->sc.dev, &b->copy));
+	for (int i = 0; i < 64; ++i) {
+		CHECK(g_pool.event(b->sc.dev, false, &b->emit_ev[i]));
+		CHECK(g_pool.event(b->sc.dev, true, &b->fo_ev[i][0]));
+		CHECK(g_pool.event(b->sc.dev, true, &b->fo_ev[i][1]));
+	}
+	CHECK(hipHostMalloc((void **)&b->err_host, 16, hipHostMallocDefault));
+	b->devout = true;
+	return 0;
+}
+
+extern "C" int m2dec_amd_hip_backend_emit(const m2r_backend_t *be, int slot, const int16_t crop[4],
+                                          const m2dec_amd_devout_t *cfg, void *dst_dev)
+{
+	HipBackend *b = hip_backend_of(be);
+	if (!b || !b->devout || slot < 0 || slot >= b->nframes || !dst_dev) return -1;
+	if (!b->stg[slot] || !b->slot_pending[slot]) {
+		fprintf(stderr, "m2dec_amd: emit: frame %d holds no picture\n", slot);
+		return -1;
+	}
+	CHECK(hipSetDevice(b->sc.dev));
+	if (b->fo_timed[slot] && hipEventQuery(b->fo_ev[slot][1]) == hipSuccess) fo_collect(b, slot);
+	CHECK(hipStreamWaitEvent(b->copy, b->slot_ev[slot], 0)); /* the picture's copy into the staging */
+	const bool timed = b->timing && !b->fo_timed[slot];
+	if (timed) CHECK(hipEventRecord(b->fo_ev[slot][0], b->copy));
+	if (m2r_frame_out_launch(b->copy, b->stg[slot], b->sc.W, b->sc.H, crop, cfg, (uint8_t *)dst_dev) < 0) return -1;
+	if (timed) {
+		CHECK(hipEventRecord(b->fo_ev[slot][1], b->copy));
+		std::lock_guard<std::mutex> lk(b->fo_mu);
+		b->fo_timed[slot] = true;
+	}
+	CHECK(hipEventRecord(b->emit_ev[slot], b->copy));
+	b->emit_pending[slot] = true;
+	return 0;
+}
+
+extern "C" int m2dec_amd_hip_backend_finish(const m2r_backend_t *be)
+{
+	HipBackend *b = hip_backend_of(be);
+	if (!b || !b->devout) return -1;
+	CHECK(hipSetDevice(b->sc.dev));
+	/* every conversion waited for its picture's copy, and that for its kernel: the copy stream's end is the end
+	 * of everything emitted; the error word behind it, into the pinned word */
+	CHECK(hipMemcpyAsync(b->err_host, b->sc.err, 2 * sizeof(int), hipMemcpyDeviceToHost, b->copy));
+	CHECK(hipStreamSynchronize(b->copy));
+	for (int i = 0; i < 64; ++i) fo_collect(b, i);
+	if (b->err_host[0]) {
+		fprintf(stderr, "m2dec_amd: wavefront hand-off failed (err=%d)\n", b->err_host[0]);
+		return -1;
+	}
+	return 0;
+}
+
+extern "C" int m2dec_amd_frame_out_timing(double *kernel_us, int64_t *frames, int reset)
+{
+	std::lock_guard<std::mutex> lk(g_fo_mu);
+	if (kernel_us) *kernel_us = g_fo_us;
+	if (frames) *frames = g_fo_frames;
+	if (reset) {
+		g_fo_us = 0;
+		g_fo_frames = 0;
+	}
+	return 0;
+}
+
 extern "C" void h264_async_pool_release(void);
 extern "C" long long h264_async_pinned_bytes(long long *pooled);
 
@@ -1874,11 +2040,11 @@ extern "C" void m2dec_amd_release_pools(void)
 		g_stage.free_blocks.clear();
 		g_stage.kept = 0;
 	}
-	{
-		std::lock_guard<std::mutex> lk(g_dev.mu);
-		for (auto &bl : g_dev.blocks) (void)hipFree(bl.p);
-		g_dev.blocks.clear();
-		g_dev.kept = 0;
+	for (DevPool *dp : {&g_dev, (DevPool *)&g_dstage}) {
+		std::lock_guard<std::mutex> lk(dp->mu);
+		for (auto &bl : dp->blocks) (void)hipFree(bl.p);
+		dp->blocks.clear();
+		dp->kept = 0;
 	}
 }
 

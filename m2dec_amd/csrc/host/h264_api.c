@@ -18,6 +18,7 @@
 #include <time.h>
 #include "h264_dec.h"
 #include "m2dec_amd.h"
+#include "frame_out.h"
 
 static int hdr_dummy(void *a, void *b)
 {
@@ -613,11 +614,34 @@ typedef struct {
 	double t_last;           /* on_frame of the last frame returned */
 	void (*on_frame)(void *arg, const m2d_frame_t *f);
 	void *arg;
+	/* device output (m2dec_amd_decode_stream_device): the frames go out on the device, the decoder's host
+	 * frames are placeholders (one distinct address each: a frame's slot is found from its luma pointer) */
+	const m2dec_amd_devout_t *dv;
+	int dv_index, dv_failed;
+	uint8_t place[H264D_MAX_FRAME_NUM][2];
 } driver_t;
+
+/* device output: ask the caller where frame `dv_index` goes, then enqueue its conversion out of the slot's
+ * device staging (complete at m2dec_amd_hip_backend_finish) */
+static void emit_device(driver_t *v, const m2d_frame_t *f)
+{
+	int slot = -1, cw, ch;
+	void *dst;
+	if (v->dv_failed) return;
+	for (int i = 0; i < v->nframes; ++i)
+		if (v->frames[i].luma == f->luma) slot = i;
+	if (slot < 0 || m2d_frame_out_geometry(f->width, f->height, f->crop, &cw, &ch) < 0) {
+		v->dv_failed = 1;
+		return;
+	}
+	dst = v->dv->frame_dst(v->dv->arg, v->dv_index++, cw, ch, m2dec_amd_frame_out_bytes(v->dv->format, cw, ch));
+	if (!dst || m2dec_amd_hip_backend_emit(&v->d->backend, slot, f->crop, v->dv, dst) < 0) v->dv_failed = 1;
+}
 
 static void emit(driver_t *v, const m2d_frame_t *f)
 {
-	if (v->on_frame) v->on_frame(v->arg, f);
+	if (v->dv) emit_device(v, f);
+	else if (v->on_frame) v->on_frame(v->arg, f);
 	v->t_last = mono_s();
 }
 
@@ -692,7 +716,15 @@ static int drv_header(void *arg, void *id)
 	luma_len = (size_t)w * (size_t)h;
 	bufnum = v->outbuf + info.frame_num + 16 + v->extra;
 	if (bufnum > H264D_MAX_FRAME_NUM) bufnum = H264D_MAX_FRAME_NUM;
-	if (v->frame_mem && bufnum <= v->nframes && luma_len <= v->luma_len) return 0;
+	if ((v->frame_mem || v->dv) && bufnum <= v->nframes && luma_len <= v->luma_len) return 0;
+	if (v->dv) { /* nothing is copied to the caller's frames: no frame memory, pinned or not */
+		for (int i = 0; i < bufnum; ++i) {
+			memset(&v->frames[i], 0, sizeof(v->frames[i]));
+			v->frames[i].luma = &v->place[i][0];
+			v->frames[i].chroma = &v->place[i][1];
+		}
+		goto set;
+	}
 	if (v->hold) m2dec_hold_wait_idle(v->hold); /* nobody reads the old frames any more */
 	fpool_give(v->frame_mem, v->frame_size);
 	v->frame_mem = fpool_take(((luma_len * 3 / 2 + 4095) & ~(size_t)4095) * (size_t)bufnum, &v->frame_size);
@@ -708,6 +740,7 @@ static int drv_header(void *arg, void *id)
 			v->frames[i].chroma = v->frames[i].luma + luma_len;
 		}
 	}
+set:
 	v->nframes = bufnum;
 	v->luma_len = luma_len;
 	{
@@ -746,10 +779,34 @@ int m2dec_amd_decode_stream3(const uint8_t *data, size_t len, const m2r_backend_
 /* the stream driver; `hold`: on_frame may keep reading a frame after it returns until it releases it
  * from `hold` (the frame is not reused meanwhile), with `extra` more frames than the decoder needs;
  * on_end (optional): called after the last frame, before the held frames are waited for */
+static int stream_core(const uint8_t *data, size_t len, const m2r_backend_t *backend, int device, int dpb,
+                       int parse_threads, int extra, m2dec_hold_t *hold,
+                       void (*on_frame)(void *arg, const m2d_frame_t *f), void (*on_end)(void *arg), void *arg,
+                       const m2dec_amd_devout_t *dv, m2dec_amd_stats_t *stats);
+
 int h264_decode_stream_held(const uint8_t *data, size_t len, const m2r_backend_t *backend, int device, int dpb,
                             int parse_threads, int extra, m2dec_hold_t *hold,
                             void (*on_frame)(void *arg, const m2d_frame_t *f), void (*on_end)(void *arg), void *arg,
                             m2dec_amd_stats_t *stats)
+{
+	return stream_core(data, len, backend, device, dpb, parse_threads, extra, hold, on_frame, on_end, arg, NULL, stats);
+}
+
+/* The stream driver with the frames delivered on the device: a HIP back end in device-output mode, owned by the
+ * context; the decode loop and the output order are the host driver's. */
+int m2dec_amd_decode_stream_device(const uint8_t *data, size_t len, int device, int dpb, const m2dec_amd_devout_t *out,
+                                   m2dec_amd_stats_t *stats)
+{
+	m2d_fo_coef_t k;
+	if (!data || !out || out->size < sizeof(*out) || !out->frame_dst || m2d_frame_out_coefs(out, &k) < 0) return -1;
+	return stream_core(data, len, NULL, device, dpb, -1, 0, NULL, NULL, NULL, NULL, out, stats);
+}
+
+/* dv: device output (backend NULL; see emit_device) */
+static int stream_core(const uint8_t *data, size_t len, const m2r_backend_t *backend, int device, int dpb,
+                       int parse_threads, int extra, m2dec_hold_t *hold,
+                       void (*on_frame)(void *arg, const m2d_frame_t *f), void (*on_end)(void *arg), void *arg,
+                       const m2dec_amd_devout_t *dv, m2dec_amd_stats_t *stats)
 {
 	driver_t v;
 	void *ctx = calloc(1, h264d_func->context_size);
@@ -770,9 +827,25 @@ int h264_decode_stream_held(const uint8_t *data, size_t len, const m2r_backend_t
 		return -1;
 	}
 	v.d = d;
+	v.dv = dv;
 	d->hold = hold;
 	d->device = device;
 	if (backend) m2dec_amd_h264_set_backend(ctx, backend);
+	if (dv) {
+		m2r_backend_t be;
+		memset(&be, 0, sizeof(be));
+		if (m2dec_amd_hip_backend_create(&be, device) < 0 || m2dec_amd_hip_backend_set_device_output(&be, 1) < 0) {
+			if (be.destroy) be.destroy(be.self);
+			m2dec_amd_h264_release(ctx);
+			free(ctx);
+			return -1;
+		}
+		m2dec_amd_h264_set_backend(ctx, &be); /* (the context owns it: destroyed with the context) */
+		if (parse_threads < 0) { /* an installed back end defaults to none: here the product path's default */
+			const char *e = getenv("M2DEC_AMD_PARSE_THREADS");
+			parse_threads = e ? atoi(e) : m2d_cpu_share();
+		}
+	}
 	if (parse_threads >= 0) m2dec_amd_h264_set_parse_threads(ctx, parse_threads);
 	dec_bits_set_callback(h264d_func->stream_pos(ctx), drv_reread, &v);
 	const double t_start = mono_s();
@@ -808,6 +881,10 @@ int h264_decode_stream_held(const uint8_t *data, size_t len, const m2r_backend_t
 	}
 done:
 	if (on_end) on_end(arg);
+	if (dv) { /* every frame complete and visible to any stream; the kernels' error word checked */
+		if ((d->have_backend && m2dec_amd_hip_backend_finish(&d->backend) < 0) || v.dv_failed) err = -1;
+		v.t_last = mono_s();
+	}
 	if (d->stats) fprintf(stderr, "stream: %d frames, %.3f s\n", n, mono_s() - t_start);
 	if (stats && !backend && d->have_backend) {
 		m2dec_amd_hip_timing_t t;
