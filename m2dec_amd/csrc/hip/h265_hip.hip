@@ -4,29 +4,37 @@
  * It restates the reference decoder's reconstruction (h265.cpp:1693-2913 intra prediction and residual,
  * :4125-4384 deblocking, :4386-4729 SAO), exactly as oracle/h265_oracle.c does on the CPU.
  *
- * k_h265_intra — the transform blocks in decoding order, one 64-lane wave (= one workgroup) at a time,
- *   persistent: a wave takes the next block from a counter, waits until the blocks that own its
- *   neighbour samples are done (the 4x4-unit owner map: one lane per neighbour unit, at most 33), then
- *   predicts (reference samples gathered straight from the frame with the substitution folded into a
- *   clamp — the available samples of a block always form one run of the substitution order —, [1 2 1] /
- *   strong smoothing in LDS, planar / DC / angular per sample), inverse-transforms the residual in LDS
- *   (DCT 4..32 / DST 4 as two matrix passes with the int16 clip between, the reference's DC-only and
- *   transform-skip shortcuts), adds, stores, releases and raises the block's done flag.  Luma and chroma
- *   blocks are independent chains and run side by side; the dependency graph, not the CTU raster, bounds
- *   the picture (a block starts as soon as its left / top / top-right / bottom-left owners are done).
+ * One picture is this chain of launches on one HIP stream (h_submit):
+ * k_h265_upload — the picture's records from its page-locked arena into device memory, the stream's scratch
+ *   words (row progress, CTU index, CTU done flags) cleared in the same launch.
+ * k_h265_mc — P / B pictures: one 64-lane workgroup per prediction block (grid-stride),
+ *   each list's reference window ((w + 7) x (h + 7) luma bytes, (w / 2 + 3) x (h / 2 + 3) CbCr pairs, positions
+ *   clamped to the picture as the reference's address_umv does) staged in LDS, then every sample computed
+ *   from LDS: the 8-tap luma filters (1-D with shift - 6, 2-D through int16 horizontal sums) and the
+ *   reference's packed two-component chroma arithmetic in 64-bit integers, bi-prediction averaged through an
+ *   int16 LDS buffer.  The CTU kernels then start each CTU from these samples and add the residuals.
+ * k_h265_ctu_index — the first record of every CTU (records are in decoding order, CTUs in raster order).
+ * k_h265_ctu_rows<NT> — intra pictures (and every picture under M2DEC_AMD_H265_CTU_GRID=0): one workgroup per CTU
+ *   row, CTUs left to right, each reconstructed entirely in an LDS tile (its samples, the column left of it,
+ *   the row above it up to the end of the above-right CTU).  A CTU waits on the row above's progress word only
+ *   if one of its intra blocks reads that row: a 2-CTU-lag wavefront, half a CTU with 64 x 64 CTBs.
+ * k_h265_ctu_grid<NT> — P / B pictures: one workgroup per CTU.  A CTU whose edge intra blocks read neighbour
+ *   CTUs first adds its inter blocks' residuals, then polls those CTUs' done flags (lower raster indices, i.e.
+ *   workgroups dispatched earlier), then reconstructs its intra blocks.
+ *   Both CTU kernels run a block on one wave: NT = 256 two waves per plane taking the plane's blocks in
+ *   decoding order behind LDS done flags (ctu_blocks), NT = 128 (M2DEC_AMD_H265_WAVES=2) one wave per plane.
+ *   A block: the residual in registers (4 x 4 / 8 x 8 by DPP / swizzle, 16 x 16 / 32 x 32 on the matrix cores,
+ *   h265_mfma.h; the reference's DC-only and transform-skip shortcuts), reference samples gathered from the tile
+ *   with the substitution folded into a clamp — the available samples of a block always form one run of the
+ *   substitution order — and [1 2 1] / strong smoothing in the same pass, planar / DC / angular per sample, the
+ *   sum clipped into the tile.  A finished CTU goes out as 32-bit write-through words, then its flag.
  * k_h265_deblock — one thread per 4-sample edge segment on the 8x8 grid, vertical edges of the whole
  *   picture, then (second launch) horizontal edges: HEVC's edges 8 samples apart never touch the same
  *   sample, so every segment of a direction is independent.  Chroma rides on the luma segment (bS 2,
  *   16-sample grid).
  * k_h265_sao — one thread per 4 bytes of an NV12 row, from a copy of the deblocked frame, dword stores.
- * k_h265_mc — P / B pictures, before the blocks: one 64-lane workgroup per prediction block (grid-stride),
- *   each list's reference window ((w + 7) x (h + 7) luma bytes, (w / 2 + 3) x (h / 2 + 3) CbCr pairs, positions
- *   clamped to the picture as the reference's address_umv does) staged in LDS, then every sample computed
- *   from LDS: the 8-tap luma filters (1-D with shift - 6, 2-D through int16 horizontal sums) and the
- *   reference's packed two-component chroma arithmetic in 64-bit integers, bi-prediction averaged through an
- *   int16 LDS buffer.  The CTU kernel then starts each CTU from these samples and adds the residuals.
- * Bounds: the intra kernel is latency-bound on the block chain (a 32x32 block is a 2 x 32^3 MAC inverse
- * transform on one wave); deblocking and SAO are HBM-bound (each reads and writes the frame once).
+ * Bounds: the CTU kernels are latency-bound on the chain of CTUs (and, inside a CTU, of intra blocks) that read
+ * each other's samples; deblocking and SAO are HBM-bound (each reads and writes the frame once).
  */
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -53,15 +61,13 @@ typedef int __attribute__((address_space(1))) gi32;
 struct H265Args {
 	const h265r_tu_t *tu;
 	const int16_t *coef;
-	const int32_t *map;
+	const int32_t *map; /* the 4 x 4 owner map: still uploaded, read by no kernel (open follow-up) */
 	const uint8_t *bs_v, *bs_h;
 	const h265r_sao_t *sao;
 	uint8_t *frame;   /* NV12, stride W */
 	uint8_t *copy;    /* the deblocked frame (SAO input) */
-	int *done;        /* per block (block kernel) */
-	int *counter;     /* next block (block kernel) */
-	int *progress;    /* per CTU row: CTUs finished (CTU kernel) */
-	int *ctu_first;   /* [ctu_cols * ctu_rows + 1]: the first record of each CTU (CTU kernel) */
+	int *progress;    /* per CTU row: half CTUs finished (row kernel) */
+	int *ctu_first;   /* [ctu_cols * ctu_rows + 1]: the first record of each CTU; behind it the CTUs' done flags (grid kernel) */
 	int ctu_cols, ctu_rows;
 	int *err;         /* sticky: a hand-off that never came */
 	int W, H, pic_w, pic_h, ctb_log2, n_tu, flags;
@@ -129,18 +135,6 @@ __device__ __forceinline__ int dct32_coef(int k, int n)
 	}
 	return sign * c_cos[m];
 }
-
-/* wave-private LDS of one block */
-struct Lds {
-	int16_t seq[2][132];   /* reference samples per component: [0 .. 4n] substitution order, filtered */
-	int16_t raw[132];      /* unfiltered copy (filter input) */
-	int16_t mat32[32 * 32]; /* the 32-point DCT matrix (built once per workgroup) */
-	int16_t mat[32 * 32];  /* transform matrix of this block's size: mat[k * n + s]; the butterfly's first-pass output */
-	int16_t t0[32 * 32];   /* coefficients, then the first-stage output */
-	int16_t pred[2][32 * 32]; /* prediction, then prediction + residual, saturated to int16 (the store clamps to
-	                           * 0..255: clamp(sat16(x)) == clamp(x)); the CTU kernels' small blocks: the residual.
-	                           * int16 keeps a wave's LDS at ~11 KB: the 4-wave CTU kernels fit two per CU */
-};
 
 /* wave-private LDS of the CTU kernels' blocks: only the reference samples — the transforms stay in registers
  * (4 x 4 / 8 x 8: cross-lane DPP / swizzle, small_block; 16 x 16 / 32 x 32: the matrix cores, big_block) */
@@ -231,285 +225,6 @@ __device__ __forceinline__ void wsync()
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-/* One pass of the N-point inverse DCT (N = 8, 16, 32) over all N lines of a block, even / odd split:
- * out[b] = E + O and out[N - 1 - b] = E - O with E / O the sums over the even / odd frequencies j of
- * T[j][b] in[j] (T[j][N - 1 - b] = (-1)^j T[j][b]), exactly the matrix product's integers in half the
- * multiplies.  Lane: line a = lane & (N - 1) (its N inputs held in registers), output pairs b =
- * (lane >> log2 N) + k 64 / N.  COLS: pass 1 (line = column x: in[j] = src[j][x], out to dst[b][x] as
- * sat16((v + 64) >> 7)); else pass 2 (line = row y: in[j] = src[y][j], dst[y][b] += sat16((v + 2048) >> 12)). */
-template <int N, bool COLS, bool ACC = true>
-__device__ __forceinline__ void idct_pass(const int16_t *src, int16_t *dst, const int16_t *mat32, int lane)
-{
-	constexpr int L = N == 8 ? 3 : (N == 16 ? 4 : 5), PAIRS = N * N / 2, PPL = PAIRS < 64 ? 1 : PAIRS / 64;
-	const int a = lane & (N - 1);
-	int in[N];
-#pragma unroll
-	for (int j = 0; j < N; ++j) in[j] = COLS ? src[j * N + a] : src[a * N + j];
-#pragma unroll
-	for (int k = 0; k < PPL; ++k) {
-		const int b = (lane >> L) + k * (64 >> L);
-		if (b < N / 2) {
-			int e = 0, o = 0;
-#pragma unroll
-			for (int j = 0; j < N; j += 2) {
-				e += mat32[(j << (5 - L)) * 32 + b] * in[j];
-				o += mat32[((j + 1) << (5 - L)) * 32 + b] * in[j + 1];
-			}
-			if (COLS) {
-				dst[b * N + a] = sat16((e + o + 64) >> 7);
-				dst[(N - 1 - b) * N + a] = sat16((e - o + 64) >> 7);
-			} else if (ACC) {
-				dst[a * N + b] = (int16_t)sat16(dst[a * N + b] + sat16((e + o + 2048) >> 12));
-				dst[a * N + N - 1 - b] = (int16_t)sat16(dst[a * N + N - 1 - b] + sat16((e - o + 2048) >> 12));
-			} else {
-				dst[a * N + b] = sat16((e + o + 2048) >> 12);
-				dst[a * N + N - 1 - b] = sat16((e - o + 2048) >> 12);
-			}
-		}
-	}
-}
-
-template <int N, bool ACC = true>
-__device__ __forceinline__ void idct_block(int16_t *t0, int16_t *tmp, int16_t *pred, const int16_t *mat32, int lane)
-{
-	idct_pass<N, true>(t0, tmp, mat32, lane);
-	wsync();
-	idct_pass<N, false, ACC>(tmp, pred, mat32, lane);
-	wsync();
-}
-
-/* samples straight from / to the frame (block kernel) */
-struct FrameSamples {
-	const H265Args &a;
-	__device__ int ld(int plane, int comp, int x, int y) const { return ld_px(a, plane, comp, x, y); }
-	/* 4 luma samples / 2 CbCr pairs of one row, little-endian in v */
-	__device__ void st(int plane, int x, int y, uint32_t v) const { st_word(plane_px(a, plane, 0, x, y), v); }
-};
-
-/* one block (wave-wide); Src: where neighbour samples come from and the block's samples go */
-template <class Src>
-__device__ void do_block(const H265Args &a, const h265r_tu_t &t, Lds &s, int lane, const Src &src, const int16_t *cbase, uint32_t clo)
-{
-	const int n = 1 << t.log2, log2 = t.log2, n2 = n * n;
-	const int ncomp = t.plane ? 2 : 1;
-	const bool luma = t.plane == 0;
-	/* ---- prediction */
-	for (int c = 0; c < ncomp; ++c) {
-		int16_t *pred = s.pred[c];
-		if (!(t.flags & H265R_TU_PRED)) {
-			for (int i = lane; i < n2; i += 64) pred[i] = src.ld(t.plane, c, t.x + (i & (n - 1)), t.y + (i >> log2));
-			continue;
-		}
-		const int at = t.avail_top > 2 * n ? 2 * n : t.avail_top, al = t.avail_left > 2 * n ? 2 * n : t.avail_left;
-		const bool top = at > 0, left = al > 0;
-		/* the available run [lo, hi] of the substitution order p[-1][2n-1] .. corner .. p[2n-1][-1] */
-		const int corner = 2 * n;
-		const int lo = left ? corner - al : (top ? corner + 1 : 0);
-		const int hi = top ? corner + at : (left ? corner - 1 : 0);
-		for (int i = lane; i <= 4 * n; i += 64) {
-			int v = 128;
-			if (top || left) {
-				const int k = clampi(i, lo, hi);
-				const int xx = k < corner ? -1 : (k == corner ? -1 : k - corner - 1);
-				const int yy = k < corner ? corner - 1 - k : -1;
-				v = src.ld(t.plane, c, t.x + xx, t.y + yy);
-			}
-			s.raw[i] = (int16_t)v;
-		}
-		wsync();
-		const int mode = t.mode;
-		bool filt = false;
-		if (luma && mode != 1 && n != 4) {
-			const int d26 = abs(mode - 26), d10 = abs(mode - 10);
-			const int dist = d26 < d10 ? d26 : d10;
-			const int thres = n == 8 ? 7 : (n == 16 ? 1 : 0);
-			filt = mode == 0 || dist > thres;
-		}
-		const int last = 4 * n;
-		bool strong = false;
-		if (filt && t.strong && n == 32) {
-			const int cc = s.raw[corner], bl = s.raw[0], tr = s.raw[last];
-			strong = abs(cc + tr - 2 * s.raw[corner + n]) < 8 && abs(cc + bl - 2 * s.raw[corner - n]) < 8;
-		}
-		for (int i = lane; i <= last; i += 64) {
-			int v = s.raw[i];
-			if (strong) {
-				const int cc = s.raw[corner];
-				if (i > 0 && i < corner) v = ((63 - (corner - 1 - i)) * cc + (corner - i) * s.raw[0] + 32) >> 6;
-				else if (i > corner && i < last) v = ((63 - (i - corner - 1)) * cc + (i - corner) * s.raw[last] + 32) >> 6;
-			} else if (filt && i > 0 && i < last) {
-				v = (s.raw[i - 1] + 2 * s.raw[i] + s.raw[i + 1] + 2) >> 2;
-			}
-			s.seq[c][i] = (int16_t)v;
-		}
-		wsync();
-		const int16_t *q = s.seq[c];
-#define LL(yy) ((int)q[corner - 1 - (yy)]) /* p[-1][y], y >= -1 */
-#define TT(xx) ((int)q[corner + 1 + (xx)]) /* p[x][-1], x >= -1 */
-		if (mode == 0) {
-			for (int i = lane; i < n2; i += 64) {
-				const int x = i & (n - 1), y = i >> log2;
-				pred[i] = ((n - 1 - x) * LL(y) + (x + 1) * TT(n) + (n - 1 - y) * TT(x) + (y + 1) * LL(n) + n) >> (log2 + 1);
-			}
-		} else if (mode == 1) {
-			int sum = 0;
-			for (int i = lane; i < n; i += 64) sum += TT(i) + LL(i);
-			for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-			const int dc = (sum + n) >> (log2 + 1);
-			for (int i = lane; i < n2; i += 64) {
-				const int x = i & (n - 1), y = i >> log2;
-				int v = dc;
-				if (luma && n < 32) {
-					if (x == 0 && y == 0) v = (LL(0) + 2 * dc + TT(0) + 2) >> 2;
-					else if (y == 0) v = (TT(x) + 3 * dc + 2) >> 2;
-					else if (x == 0) v = (LL(y) + 3 * dc + 2) >> 2;
-				}
-				pred[i] = v;
-			}
-		} else {
-			const int ang = c_ang[mode], inv = c_inv[mode];
-			const bool vert = mode >= 18;
-			for (int i = lane; i < n2; i += 64) {
-				const int x = i & (n - 1), y = i >> log2;
-				const int p = vert ? y : x, qq = vert ? x : y;
-				const int idx = ((p + 1) * ang) >> 5, fr = ((p + 1) * ang) & 31;
-				int r1, r2;
-				{
-					const int k = qq + idx + 1;
-					int kk = k;
-					if (kk >= 0) r1 = vert ? TT(kk - 1) : LL(kk - 1);
-					else r1 = vert ? LL(-1 + ((kk * inv + 128) >> 8)) : TT(-1 + ((kk * inv + 128) >> 8));
-					kk = k + 1;
-					if (kk >= 0) r2 = vert ? TT(kk - 1) : LL(kk - 1);
-					else r2 = vert ? LL(-1 + ((kk * inv + 128) >> 8)) : TT(-1 + ((kk * inv + 128) >> 8));
-				}
-				int v = fr ? ((32 - fr) * r1 + fr * r2 + 16) >> 5 : r1;
-				if (luma && n < 32) {
-					if (mode == 26 && x == 0) v = clampi(TT(0) + ((LL(y) - LL(-1)) >> 1), 0, 255);
-					if (mode == 10 && y == 0) v = clampi(LL(0) + ((TT(x) - TT(-1)) >> 1), 0, 255);
-				}
-				pred[i] = v;
-			}
-		}
-#undef LL
-#undef TT
-		wsync();
-	}
-	/* ---- residual */
-	for (int c = 0; c < ncomp; ++c) {
-		const int kind = t.res[c];
-		int16_t *pred = s.pred[c];
-		if (kind == H265R_RES_NONE) continue;
-		const int16_t *d = cbase + (t.coef[c] - clo); /* (the pool, or the CTU's coefficients staged in LDS) */
-		if (kind == H265R_RES_DC) {
-			const int dc = (d[0] + 64) >> 7; /* acNxNtransform_dconly<N, 7> (m2d.h:306-341) */
-			for (int i = lane; i < n2; i += 64) pred[i] = (int16_t)sat16(pred[i] + dc);
-			continue;
-		}
-		if (kind == H265R_RES_SKIP) {
-			for (int i = lane; i < n2; i += 64) pred[i] = (int16_t)sat16(pred[i] + ((d[i] + 16) >> 5));
-			continue;
-		}
-		for (int i = lane; i < n2; i += 64) s.t0[i] = d[i];
-		const bool dstm = kind == H265R_RES_DST;
-		if (!dstm && n >= 8) {
-			wsync();
-			if (n == 8) idct_block<8>(s.t0, s.mat, pred, s.mat32, lane);
-			else if (n == 16) idct_block<16>(s.t0, s.mat, pred, s.mat32, lane);
-			else idct_block<32>(s.t0, s.mat, pred, s.mat32, lane);
-			continue;
-		}
-		for (int i = lane; i < n2; i += 64) {
-			const int k = i >> log2, sm = i & (n - 1);
-			s.mat[i] = dstm ? c_dst[k * 4 + sm] : s.mat32[(k << (5 - log2)) * 32 + sm];
-		}
-		wsync();
-		/* first stage (columns): g[y][x] = sat16((sum_j M[j][y] d[j][x] + 64) >> 7) */
-		int g[16];
-		for (int r = 0, i = lane; i < n2; i += 64, ++r) {
-			const int x = i & (n - 1), y = i >> log2;
-			int e = 0;
-			for (int j = 0; j < n; ++j) e += s.mat[j * n + y] * s.t0[j * n + x];
-			g[r] = sat16((e + 64) >> 7);
-		}
-		wsync();
-		for (int r = 0, i = lane; i < n2; i += 64, ++r) s.t0[i] = g[r];
-		wsync();
-		/* second stage (rows): r[y][x] = sat16((sum_j M[j][x] g[y][j] + 2048) >> 12) */
-		for (int i = lane; i < n2; i += 64) {
-			const int x = i & (n - 1), y = i >> log2;
-			int e = 0;
-			for (int j = 0; j < n; ++j) e += s.mat[j * n + x] * s.t0[y * n + j];
-			pred[i] = (int16_t)sat16(pred[i] + sat16((e + 2048) >> 12));
-		}
-		wsync();
-	}
-	/* ---- out: 32-bit write-through words (luma: 4 samples of a row; chroma: 2 CbCr pairs) */
-	if (luma) {
-		const int wpr = n >> 2;
-		for (int w = lane; w < n2 >> 2; w += 64) {
-			const int y = w / wpr, x = (w - y * wpr) * 4;
-			const int16_t *q = s.pred[0] + y * n + x;
-			const uint32_t v = (uint32_t)clampi(q[0], 0, 255) | ((uint32_t)clampi(q[1], 0, 255) << 8) |
-			                   ((uint32_t)clampi(q[2], 0, 255) << 16) | ((uint32_t)clampi(q[3], 0, 255) << 24);
-			src.st(0, t.x + x, t.y + y, v);
-		}
-	} else {
-		const int wpr = n >> 1;
-		for (int w = lane; w < n2 >> 1; w += 64) {
-			const int y = w / wpr, x = (w - y * wpr) * 2;
-			const int16_t *cb = s.pred[0] + y * n + x, *cr = s.pred[1] + y * n + x;
-			const uint32_t v = (uint32_t)clampi(cb[0], 0, 255) | ((uint32_t)clampi(cr[0], 0, 255) << 8) |
-			                   ((uint32_t)clampi(cb[1], 0, 255) << 16) | ((uint32_t)clampi(cr[1], 0, 255) << 24);
-			src.st(1, t.x + x, t.y + y, v);
-		}
-	}
-}
-
-__global__ __launch_bounds__(64) void k_h265_intra(const H265Args *ap)
-{
-	const H265Args a = *ap;
-	__shared__ Lds s;
-	const int lane = threadIdx.x;
-	for (int i = lane; i < 32 * 32; i += 64) s.mat32[i] = (int16_t)dct32_coef(i >> 5, i & 31);
-	__syncthreads();
-	for (;;) {
-		const int v = __hip_atomic_fetch_add((gi32 *)&a.counter[0], lane == 0 ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		const int idx = __builtin_amdgcn_readfirstlane(v);
-		if (idx >= a.n_tu) break;
-		const h265r_tu_t t = a.tu[idx];
-		/* wait for the owners of the neighbour samples: lane k < 2n/4 the top units, next the left units, last the corner */
-		{
-			const int n = 1 << t.log2;
-			const int at = t.avail_top > 2 * n ? 2 * n : t.avail_top, al = t.avail_left > 2 * n ? 2 * n : t.avail_left;
-			const int ntop = at > 0 ? (at + 3) >> 2 : 0, nleft = al > 0 ? (al + 3) >> 2 : 0;
-			const int mw = t.plane ? a.W / 8 : a.W / 4;
-			const int32_t *map = a.map + (t.plane ? (size_t)(a.W / 4) * (a.H / 4) : 0);
-			int dep = -1;
-			if (lane < ntop) dep = map[(size_t)((t.y >> 2) - 1) * mw + (t.x >> 2) + lane];
-			else if (lane < ntop + nleft) dep = map[(size_t)((t.y >> 2) + lane - ntop) * mw + (t.x >> 2) - 1];
-			else if (lane == ntop + nleft && ntop && nleft) dep = map[(size_t)((t.y >> 2) - 1) * mw + (t.x >> 2) - 1];
-			unsigned spins = 0;
-			for (;;) {
-				const bool ok = dep < 0 || dep >= idx ||
-				                __hip_atomic_load((gi32 *)&a.done[dep], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-				if (__all(ok)) break;
-				if (++spins > H265_SPIN_LIMIT) {
-					__hip_atomic_store((gi32 *)a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					break;
-				}
-				if (__hip_atomic_load((gi32 *)a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-				__builtin_amdgcn_s_sleep(1);
-			}
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); /* keeps the sample loads below the poll */
-		}
-		do_block(a, t, s, lane, FrameSamples{a}, a.coef, 0);
-		/* publish: the write-through sample stores drained, then the flag */
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		__hip_atomic_store((gi32 *)&a.done[idx], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	}
-}
-
 /* ---- the CTU wavefront (default): one workgroup per CTU row, CTUs left to right; wave 0 reconstructs the
  * CTU's luma blocks, wave 1 its chroma blocks, each in decoding order, entirely in LDS: the CTU's samples,
  * the column left of it (kept from the previous CTU) and the row above it from the left-above corner to
@@ -525,25 +240,6 @@ struct CtuTile {
 	uint8_t ly[H265_CTB_MAX], lc[H265_CTB_MAX];  /* the column left of the CTU (CbCr pairs) */
 	uint8_t ty[2 * H265_CTB_MAX + 4];            /* the row above: [0] the left-above corner, [1 + i] x0 + i */
 	uint8_t tc[2 * H265_CTB_MAX + 4];            /* CbCr pairs: [2 (1 + i) + comp] */
-};
-
-struct CtuSamples {
-	CtuTile &tl;
-	int x0, y0; /* the CTU's luma origin */
-	__device__ int ld(int plane, int comp, int x, int y) const
-	{
-		if (!plane) {
-			const int dx = x - x0, dy = y - y0;
-			return dy < 0 ? tl.ty[dx + 1] : (dx < 0 ? tl.ly[dy] : tl.y[dy][dx]);
-		}
-		const int dx = x - (x0 >> 1), dy = y - (y0 >> 1);
-		return dy < 0 ? tl.tc[2 * (dx + 1) + comp] : (dx < 0 ? tl.lc[2 * dy + comp] : tl.c[dy][2 * dx + comp]);
-	}
-	__device__ void st(int plane, int x, int y, uint32_t v) const
-	{
-		if (!plane) *(uint32_t *)&tl.y[y - y0][x - x0] = v;
-		else *(uint32_t *)&tl.c[y - (y0 >> 1)][2 * (x - (x0 >> 1))] = v;
-	}
 };
 
 /* the record with every field in scalar registers (all lanes read the same LDS record: without this the
@@ -786,10 +482,9 @@ __device__ void big_block(const h265r_tu_t &t, CtuTile &tl, LdsCtu &s, const h26
 	H5PH(lane, t, 3);
 }
 
-/* 4 x 4 and 8 x 8 blocks of the CTU kernels (the many: three quarters of a picture's blocks), the same integers as
- * do_block in three wave-serial phases (round-5 stamps: a 4x4 block cost ~2 us of phase latency, the CTU's ~25 luma
- * blocks one after another):
- *   1. the residual first, into s.pred (it does not depend on the prediction): full / DST transforms;
+/* 4 x 4 and 8 x 8 blocks of the CTU kernels (the many: three quarters of a picture's blocks), in three wave-serial
+ * phases (round-5 stamps: a 4x4 block cost ~2 us of phase latency, the CTU's ~25 luma blocks one after another):
+ *   1. the residual first, in registers (it does not depend on the prediction): full / DST transforms;
  *      DC-only and transform-skip are added per sample in phase 3;
  *   2. reference samples gathered AND filtered in one pass (ref_samples), both chroma components side by side;
  *   3. prediction + residual, clipped and stored straight into the tile: lane l owns sample (l & (N - 1), l >> log2 N)
@@ -1181,7 +876,7 @@ __global__ __launch_bounds__(NT, 2) void k_h265_ctu_rows(const H265Args *ap)
 		 * chunk, then any further chunk of a CTU with more than H265_CTU_RECS records */
 		if (m0 > 0)
 			ctu_blocks<NT>(a, recs, m0, tl, ls, kc, sch, tid, x0, y0, cb0, clo0, row, col, 0,
-			               m0 == i1 - i0 && row + 1 < a.ctu_rows && a.ctb_log2 == 6 && !(a.flags & (1 << 28)));
+			               m0 == i1 - i0 && row + 1 < a.ctu_rows && a.ctb_log2 == 6);
 		for (int c0 = i0 + m0; c0 < i1; c0 += H265_CTU_RECS) {
 			const int m = min(H265_CTU_RECS, i1 - c0);
 			__syncthreads(); /* (the previous chunk is consumed) */
@@ -1277,7 +972,7 @@ __global__ __launch_bounds__(NT, 2) void k_h265_ctu_grid(const H265Args *ap)
 		 * block reads only earlier blocks' samples: the inter ones are final by then): the inter work leaves the
 		 * chain of intra CTUs (r166: the neighbour waits were ~75 % of the 1080p P / B CTU pass).  A CTU with more
 		 * records than one LDS chunk keeps the single pass. */
-		const bool split = need && i1 - i0 <= H265_CTU_RECS && !(a.flags & (1 << 29));
+		const bool split = need && i1 - i0 <= H265_CTU_RECS;
 		uint32_t clo0 = 0;
 		const int16_t *cb0 = nullptr;
 		if (split) {
@@ -1288,7 +983,7 @@ __global__ __launch_bounds__(NT, 2) void k_h265_ctu_grid(const H265Args *ap)
 			ctu_blocks<NT>(a, recs, i1 - i0, tl, ls, kc, sch, tid, x0, y0, cb0, clo0, row, col, 1);
 		}
 		/* wave 0 lanes 0..3 poll one neighbour each */
-		if (wave == 0 && need && !(a.flags & (1 << 30))) {
+		if (wave == 0 && need) {
 			int dep = -1;
 			if (lane == 0 && (need & 1)) dep = c - 1;
 			if (lane == 1 && (need & 2)) dep = c - a.ctu_cols - 1;
@@ -1358,9 +1053,9 @@ __global__ __launch_bounds__(NT, 2) void k_h265_ctu_grid(const H265Args *ap)
 	if (tid == 0) __hip_atomic_store(&done[c], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-/* ---- the picture's records from the pinned arena into device memory (16 bytes per thread, grid-stride) */
-/* a copy by a kernel (records up from the pinned arena, frames down to pinned staging); `zero` (nzero ints): the
- * picture's scratch words cleared in the same launch (one HIP call fewer per picture on the serial submission) */
+/* ---- the picture's records from the pinned arena into device memory (16 bytes per thread, grid-stride); `zero`
+ * (nzero ints): the picture's scratch words cleared in the same launch (one HIP call fewer per picture on the
+ * serial submission) */
 __global__ __launch_bounds__(256) void k_h265_upload(const uint4 *src, uint4 *dst, size_t n16, int *zero, size_t nzero)
 {
 	const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
@@ -1699,7 +1394,7 @@ struct H265Gpu {
 	std::mutex amu; /* pool, staged, grave_*, max_total */
 	struct Lane {
 		uint8_t *copy = nullptr; /* the deblocked frame (SAO input) */
-		int *scratch = nullptr;  /* done flags + the block counter + CTU progress */
+		int *scratch = nullptr;  /* the CTU rows' progress words, the CTUs' first records and done flags (scratch_words) */
 		size_t scratch_n = 0;
 	} lane[NS];
 	int rr = 0;
@@ -1713,20 +1408,19 @@ struct H265Gpu {
 	long pictures = 0;
 	int64_t record_bytes = 0, frame_bytes = 0;
 	std::vector<uint8_t *> grave_host, grave_dev; /* outgrown arenas (freed at set_frames / destroy) */
-	bool block_kernel = false; /* M2DEC_AMD_H265_BLOCKS=1: the per-block dependency-graph kernel */
 	bool trace = false;        /* M2DEC_AMD_H265_TRACE */
-	bool upload_zero = true;   /* scratch cleared by the upload kernel (M2DEC_AMD_H265_UPLOAD_ZERO=0: hipMemsetAsync, A/B) */
 	double trace_ms = 0.5;     /* M2DEC_AMD_H265_TRACE_MS: the submit steps reported above this */
-	bool kcopy = true;         /* record upload by k_h265_upload (M2DEC_AMD_H265_KCOPY=0: hipMemcpyAsync) */
-	bool kcopy_d2h = false;    /* M2DEC_AMD_KCOPY_D2H=1: the frame down by k_h265_upload writing the pinned staging buffer */
 	size_t max_total = 0;      /* the largest picture's arena bytes so far */
 	bool waves4 = true;        /* CTU kernels with two waves per plane (M2DEC_AMD_H265_WAVES=2: one) */
-	bool err_async = true;     /* error word copied behind each frame (M2DEC_AMD_H265_ERR_ASYNC=0: read in sync) */
-	bool ctu_grid = true;      /* P / B pictures: one workgroup per CTU (M2DEC_AMD_H265_CTU_GRID=0: the row kernel) */
-	bool no_stage = false;     /* M2DEC_AMD_H265_STAGE=0: records copied by submit only (A/B) */
+	bool ctu_grid = true;     /* P / B pictures: one workgroup per CTU (M2DEC_AMD_H265_CTU_GRID=0: the row kernel) */
+	bool no_stage = false;     /* M2DEC_AMD_H265_STAGE=0: records copied by submit only (as for a caller without a parse pipeline) */
 };
 
 static size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+/* a lane's scratch words for a picture of rows x cols CTUs: the rows' progress words, ctu_first[nctu + 1] and the
+ * CTUs' done flags (H265Args::progress, ::ctu_first) */
+static size_t scratch_words(int rows, int cols) { return (size_t)rows + 2 * (size_t)rows * cols + 1; }
 
 static void flush_timing(H265Gpu *g, H265Gpu::Timing &t)
 {
@@ -1774,9 +1468,8 @@ int h_set_frames(void *p, int n, const m2d_frame_t *frames, int width, int heigh
 			}
 	}
 	{
-		/* scratch words of the largest picture the frame holds: 4 x 4 luma and chroma blocks, 16 x 16 CTUs */
-		const size_t sn = (size_t)(width / 4) * (height / 4) + (size_t)(width / 8) * (height / 8) + 2 + (size_t)(height / 16 + 1) +
-		                  2 * (size_t)(width / 16 + 1) * (height / 16 + 1) + 1;
+		/* scratch words of the largest picture the frame holds: 16 x 16 CTUs */
+		const size_t sn = scratch_words(height / 16 + 1, width / 16 + 1);
 		for (int k = 0; k < g->ns; ++k) {
 			H265Gpu::Lane &ln = g->lane[k];
 			if (sn <= ln.scratch_n) continue;
@@ -2029,6 +1722,204 @@ int h_stage(void *p, const h265r_picture_t *pic, int discard)
 	return 0;
 }
 
+/* ---- h_submit's steps, in the order it runs them */
+
+/* the picture's arena, reserved for the caller: the one a parse worker staged, else a free one filled here (after
+ * the checks); -1 when the picture is refused or on a HIP error */
+static int find_arena(H265Gpu *g, const h265r_picture_t *pic, ArenaLayout *L, unsigned *refs)
+{
+	int ai = -1;
+	{
+		std::lock_guard<std::mutex> lk(g->amu);
+		for (auto &e : g->staged)
+			if (staged_match(e, pic)) {
+				ai = e.arena;
+				*refs = e.refs;
+				e.arena = -1;
+				g->staged_used++;
+				break;
+			}
+	}
+	if (ai < 0 && check_picture(g, pic, refs) < 0) return -1;
+	if (hipSetDevice(g->dev) != hipSuccess) {
+		if (ai >= 0) arena_release(g, ai);
+		return -1;
+	}
+	*L = layout_of(pic);
+	if (ai < 0) {
+		ai = arena_acquire(g, L->total);
+		if (ai < 0) return -1;
+		arena_fill(g->pool[ai], pic, *L);
+	}
+	return ai;
+}
+
+/* An arena whose upload may be queued on s: its `used` event behind everything queued so far, so that
+ * arena_acquire hands it out again only once that work is done.  If the event cannot be recorded the stream is
+ * drained instead: the arena is never free under a pending upload. */
+static int arena_retire(H265Gpu *g, H265Gpu::Arena &a, hipStream_t s)
+{
+	if (hipEventRecord(a.used, s) != hipSuccess) {
+		(void)hipStreamSynchronize(s);
+		return -1;
+	}
+	std::lock_guard<std::mutex> lk(g->amu);
+	a.recorded = true;
+	a.last = ++g->arena_clock;
+	return 0;
+}
+
+/* the stream: the first idle one after the last, else round robin */
+static int pick_stream(H265Gpu *g)
+{
+	int k = g->rr;
+	for (int i = 0; i < g->ns; ++i) {
+		const int c = (g->rr + i) % g->ns;
+		if (hipStreamQuery(g->st[c]) == hipSuccess) {
+			k = c;
+			break;
+		}
+	}
+	g->rr = (k + 1) % g->ns;
+	return k;
+}
+
+/* the kernels' argument block, written behind the records in the arena; returns its device address */
+static const H265Args *build_args(const H265Gpu *g, const h265r_picture_t *pic, const ArenaLayout &L, const H265Gpu::Arena &a,
+                                  const H265Gpu::Lane &ln, uint8_t *frame)
+{
+	H265Args h;
+	h.tu = (const h265r_tu_t *)(a.dev + L.o_tu);
+	h.coef = (const int16_t *)(a.dev + L.o_coef);
+	h.map = (const int32_t *)(a.dev + L.o_map);
+	h.bs_v = a.dev + L.o_bsv;
+	h.bs_h = a.dev + L.o_bsh;
+	h.sao = (const h265r_sao_t *)(a.dev + L.o_sao);
+	h.frame = frame;
+	h.copy = ln.copy;
+	h.progress = ln.scratch;
+	h.ctu_first = h.progress + L.rows;
+	h.ctu_cols = L.cols;
+	h.ctu_rows = L.rows;
+	h.err = g->err;
+	h.W = g->W;
+	h.H = g->H;
+	h.pic_w = pic->pic_w;
+	h.pic_h = pic->pic_h;
+	h.ctb_log2 = pic->ctb_log2;
+	h.n_tu = pic->n_tu;
+	h.flags = pic->flags;
+	h.beta_offset = pic->beta_offset;
+	h.tc_offset = pic->tc_offset;
+	h.cb_qp_offset = pic->cb_qp_offset;
+	h.cr_qp_offset = pic->cr_qp_offset;
+	h.pu = (const h265r_pu_t *)(a.dev + L.o_pu);
+	h.frames = g->frames;
+	h.fsz = g->fsz;
+	h.n_pu = pic->n_pu;
+	memcpy(a.host + L.o_args, &h, sizeof(h));
+	return (const H265Args *)(a.dev + L.o_args);
+}
+
+/* the upload as a kernel reading the pinned records over the host link, the lane's scratch words cleared in the
+ * same launch: an SDMA copy queued behind an earlier picture's copy-out (itself waiting for that picture's
+ * kernels) held this thread 8-10 ms once per decode, the GPU idling meanwhile (round-5 H.265 timelines) */
+static int enqueue_upload(const H265Gpu::Arena &a, size_t total, int *scratch, size_t sn, hipStream_t s)
+{
+	const size_t n16 = total / 16;
+	const int grid = (int)std::min<size_t>(512, (n16 + 255) / 256);
+	hipLaunchKernelGGL(k_h265_upload, dim3(grid), dim3(256), 0, s, (const uint4 *)a.host_dev, (uint4 *)a.dev, n16, scratch, sn);
+	H265_CHECK(hipGetLastError());
+	return 0;
+}
+
+/* dependencies on other streams' pictures, after the upload (a copy behind a wait on another stream's picture
+ * can hold this thread until that picture completes: 8-10 ms per decode in the round-5 trace) */
+static int wait_dependencies(H265Gpu *g, int slot, unsigned refs, hipStream_t s)
+{
+	for (int r = 0; r < H265R_MAX_FRAMES; ++r)
+		if (((refs >> r) & 1) && g->kdone[r]) H265_CHECK(hipStreamWaitEvent(s, g->kdone[r], 0));
+	for (const auto &re : g->readers[slot]) H265_CHECK(hipStreamWaitEvent(s, re.second, 0));
+	if (g->kdone[slot]) H265_CHECK(hipStreamWaitEvent(s, g->kdone[slot], 0));
+	if (g->pend[slot] || g->kdone[slot]) H265_CHECK(hipStreamWaitEvent(s, g->ev[slot], 0)); /* its copy-out */
+	return 0;
+}
+
+/* motion compensation, then the CTUs: P / B pictures one workgroup per CTU, else (and under
+ * M2DEC_AMD_H265_CTU_GRID=0) one per CTU row */
+static int launch_recon(const H265Gpu *g, const h265r_picture_t *pic, const ArenaLayout &L, const H265Args *args, hipStream_t s)
+{
+	if (pic->n_pu) {
+		const int grid = pic->n_pu < g->cus * 8 ? pic->n_pu : g->cus * 8;
+		hipLaunchKernelGGL(k_h265_mc, dim3(grid), dim3(64), 0, s, args);
+		H265_CHECK(hipGetLastError());
+	}
+	if (pic->n_tu) {
+		hipLaunchKernelGGL(k_h265_ctu_index, dim3(pic->n_tu / 256 + 1), dim3(256), 0, s, args);
+		if (pic->n_pu && g->ctu_grid) {
+			if (g->waves4) hipLaunchKernelGGL(k_h265_ctu_grid<256>, dim3(L.cols * L.rows), dim3(256), 0, s, args);
+			else hipLaunchKernelGGL(k_h265_ctu_grid<128>, dim3(L.cols * L.rows), dim3(128), 0, s, args);
+		} else if (g->waves4) {
+			hipLaunchKernelGGL(k_h265_ctu_rows<256>, dim3(L.rows), dim3(256), 0, s, args);
+		} else {
+			hipLaunchKernelGGL(k_h265_ctu_rows<128>, dim3(L.rows), dim3(128), 0, s, args);
+		}
+		H265_CHECK(hipGetLastError());
+	}
+	return 0;
+}
+
+static int launch_deblock(const H265Gpu *g, const h265r_picture_t *pic, const H265Args *args, hipStream_t s)
+{
+	if (!(pic->flags & H265R_PIC_DEBLOCK)) return 0;
+	const int nv = (g->H / 4) * (g->W / 8), nh = (g->H / 8) * (g->W / 4);
+	hipLaunchKernelGGL(k_h265_deblock, dim3((nv + 255) / 256), dim3(256), 0, s, args, 0);
+	hipLaunchKernelGGL(k_h265_deblock, dim3((nh + 255) / 256), dim3(256), 0, s, args, 1);
+	H265_CHECK(hipGetLastError());
+	return 0;
+}
+
+static int launch_sao(const H265Gpu *g, const h265r_picture_t *pic, uint8_t *copy, const uint8_t *frame, const H265Args *args, hipStream_t s)
+{
+	if (!(pic->flags & (H265R_PIC_SAO_LUMA | H265R_PIC_SAO_CHROMA))) return 0;
+	H265_CHECK(hipMemcpyAsync(copy, frame, (size_t)g->W * g->H * 3 / 2, hipMemcpyDeviceToDevice, s));
+	const int nsa = (pic->pic_h + (pic->pic_h >> 1)) * (g->W >> 2); /* (4 bytes of a row per thread) */
+	hipLaunchKernelGGL(k_h265_sao, dim3((nsa + 255) / 256), dim3(256), 0, s, args);
+	H265_CHECK(hipGetLastError());
+	return 0;
+}
+
+/* this picture's kernels, on stream k: what later readers of its frame wait for, and what the next writers of
+ * its references' frames wait for */
+static int record_kernels_done(H265Gpu *g, int slot, unsigned refs, int k)
+{
+	hipEvent_t kd = next_event(g);
+	if (!kd) return -1;
+	H265_CHECK(hipEventRecord(kd, g->st[k]));
+	for (int r = 0; r < H265R_MAX_FRAMES; ++r)
+		if ((refs >> r) & 1) {
+			auto &rd = g->readers[r];
+			auto it = std::find_if(rd.begin(), rd.end(), [k](const std::pair<int, hipEvent_t> &x) { return x.first == k; });
+			if (it != rd.end()) it->second = kd;
+			else rd.emplace_back(k, kd);
+		}
+	g->readers[slot].clear();
+	g->kdone[slot] = kd;
+	return 0;
+}
+
+/* the picture to its staging buffer, behind the kernels, and behind it the sticky error word as of this frame */
+static int copy_out(H265Gpu *g, int slot, const uint8_t *frame, hipStream_t s)
+{
+	const size_t bytes = (size_t)g->W * g->H * 3 / 2;
+	if (!g->stg[slot]) H265_CHECK(hipHostMalloc((void **)&g->stg[slot], bytes, hipHostMallocDefault));
+	H265_CHECK(hipMemcpyAsync(g->stg[slot], frame, bytes, hipMemcpyDeviceToHost, s));
+	H265_CHECK(hipMemcpyAsync(&g->err_host[slot], g->err, sizeof(int), hipMemcpyDeviceToHost, s));
+	H265_CHECK(hipEventRecord(g->ev[slot], s));
+	g->pend[slot] = true;
+	return 0;
+}
+
 int h_submit(void *p, const h265r_picture_t *pic)
 {
 	H265Gpu *g = (H265Gpu *)p;
@@ -2046,197 +1937,59 @@ int h_submit(void *p, const h265r_picture_t *pic)
 		tp = t;
 	};
 	unsigned refs = 0;
-	int ai = -1;
-	{
-		std::lock_guard<std::mutex> lk(g->amu);
-		for (auto &e : g->staged)
-			if (staged_match(e, pic)) {
-				ai = e.arena;
-				refs = e.refs;
-				e.arena = -1;
-				g->staged_used++;
-				break;
-			}
-	}
-	if (ai < 0 && check_picture(g, pic, &refs) < 0) return -1;
-	H265_CHECK(hipSetDevice(g->dev));
-	const ArenaLayout L = layout_of(pic);
-	if (ai < 0) {
-		ai = arena_acquire(g, L.total);
-		if (ai < 0) return -1;
-		arena_fill(g->pool[ai], pic, L);
-	}
-	/* (the arena goes back to the pool on every return below; after its `used` event on success) */
+	ArenaLayout L;
+	const int ai = find_arena(g, pic, &L, &refs);
+	if (ai < 0) return -1;
+	/* The arena goes back to the pool on every return below.  From the upload on it is first retired on the
+	 * picture's stream, so that no return path frees it while the upload kernel may still read its pinned
+	 * memory (or a kernel its device copy): on success right behind the kernels, on an error wherever it struck. */
 	struct Release {
 		H265Gpu *g;
 		int i;
-		~Release() { arena_release(g, i); }
-	} release{g, ai};
+		hipStream_t s; /* null until the upload is about to be queued */
+		bool retired;
+		~Release()
+		{
+			if (s && !retired) (void)arena_retire(g, g->pool[i], s);
+			arena_release(g, i);
+		}
+	} release{g, ai, nullptr, false};
 	H265Gpu::Arena &a = g->pool[ai];
 	lap("records");
-	/* the stream: the first idle one after the last, else round robin */
-	int k = g->rr;
-	for (int i = 0; i < g->ns; ++i) {
-		const int c = (g->rr + i) % g->ns;
-		if (hipStreamQuery(g->st[c]) == hipSuccess) {
-			k = c;
-			break;
-		}
-	}
-	g->rr = (k + 1) % g->ns;
+	const int k = pick_stream(g);
 	hipStream_t s = g->st[k];
 	H265Gpu::Lane &ln = g->lane[k];
-	const int cols = L.cols, rows = L.rows;
-	const size_t o_tu = L.o_tu, o_coef = L.o_coef, o_map = L.o_map, o_bsv = L.o_bsv, o_bsh = L.o_bsh, o_sao = L.o_sao,
-	             o_pu = L.o_pu, o_args = L.o_args, total = L.total;
-	/* per-block done flags + 2 counters, then the CTU rows' progress words, the CTUs' first records and the CTUs'
-	 * done flags (sized for the frame at set_frames: a block is at least 4 x 4) */
-	const int nctu = cols * rows;
-	const size_t sn = (size_t)pic->n_tu + 2 + (size_t)rows + 2 * (size_t)nctu + 1;
+	const size_t sn = scratch_words(L.rows, L.cols);
 	if (sn > ln.scratch_n) return -1;
-	H265Args h;
-	h.tu = (const h265r_tu_t *)(a.dev + o_tu);
-	h.coef = (const int16_t *)(a.dev + o_coef);
-	h.map = (const int32_t *)(a.dev + o_map);
-	h.bs_v = a.dev + o_bsv;
-	h.bs_h = a.dev + o_bsh;
-	h.sao = (const h265r_sao_t *)(a.dev + o_sao);
-	h.frame = g->frames + (size_t)pic->slot * g->fsz;
-	h.copy = ln.copy;
-	h.done = ln.scratch;
-	h.counter = ln.scratch + pic->n_tu;
-	h.progress = h.counter + 2;
-	h.ctu_first = h.progress + rows;
-	h.ctu_cols = cols;
-	h.ctu_rows = rows;
-	h.err = g->err;
-	h.W = g->W;
-	h.H = g->H;
-	h.pic_w = pic->pic_w;
-	h.pic_h = pic->pic_h;
-	h.ctb_log2 = pic->ctb_log2;
-	h.n_tu = pic->n_tu;
-	h.flags = pic->flags;
-	if (getenv("M2DEC_AMD_H265_DIAG_NOWAIT")) h.flags |= 1 << 30; /* (diagnostic: CTU-grid neighbour waits skipped — wrong output) */
-	if (getenv("M2DEC_AMD_H265_GRID_ONEPASS")) h.flags |= 1 << 29; /* (A/B: no inter-first split of the CTU-grid blocks) */
-	if (getenv("M2DEC_AMD_H265_NO_HALF_ROW")) h.flags |= 1 << 28;   /* (A/B: a CTU's last row published only with the CTU) */
-	h.beta_offset = pic->beta_offset;
-	h.tc_offset = pic->tc_offset;
-	h.cb_qp_offset = pic->cb_qp_offset;
-	h.cr_qp_offset = pic->cr_qp_offset;
-	h.pu = (const h265r_pu_t *)(a.dev + o_pu);
-	h.frames = g->frames;
-	h.fsz = g->fsz;
-	h.n_pu = pic->n_pu;
-	memcpy(a.host + o_args, &h, sizeof(h));
-	const H265Args *args = (const H265Args *)(a.dev + o_args);
+	uint8_t *frame = g->frames + (size_t)pic->slot * g->fsz;
+	const H265Args *args = build_args(g, pic, L, a, ln, frame);
 	lap("record copy");
-	if (g->kcopy) {
-		/* the upload as a kernel reading the pinned records over the host link: an SDMA copy queued behind an
-		 * earlier picture's copy-out (itself waiting for that picture's kernels) held this thread 8-10 ms once
-		 * per decode, the GPU idling meanwhile (round-5 H.265 timelines) */
-		const size_t n16 = total / 16;
-		const int grid = (int)std::min<size_t>(512, (n16 + 255) / 256);
-		hipLaunchKernelGGL(k_h265_upload, dim3(grid), dim3(256), 0, s, (const uint4 *)a.host_dev, (uint4 *)a.dev, n16,
-		                   g->upload_zero ? ln.scratch : (int *)nullptr, g->upload_zero ? sn : (size_t)0);
-		H265_CHECK(hipGetLastError());
-		if (!g->upload_zero) H265_CHECK(hipMemsetAsync(ln.scratch, 0, sizeof(int) * sn, s));
-	} else {
-		H265_CHECK(hipMemcpyAsync(a.dev, a.host, total, hipMemcpyHostToDevice, s));
-		H265_CHECK(hipMemsetAsync(ln.scratch, 0, sizeof(int) * sn, s));
-	}
+	release.s = s;
+	if (enqueue_upload(a, L.total, ln.scratch, sn, s) < 0) return -1;
 	lap("upload");
-	g->record_bytes += (int64_t)o_args;
+	g->record_bytes += (int64_t)L.o_args;
 	g->frame_bytes += (int64_t)g->W * g->H * 3 / 2;
-	/* dependencies on other streams' pictures, after the uploads (a copy behind a wait on another stream's
-	 * picture can hold this thread until that picture completes: 8-10 ms per decode in the round-5 trace) */
-	for (int r = 0; r < H265R_MAX_FRAMES; ++r)
-		if (((refs >> r) & 1) && g->kdone[r]) H265_CHECK(hipStreamWaitEvent(s, g->kdone[r], 0));
-	for (const auto &re : g->readers[pic->slot]) H265_CHECK(hipStreamWaitEvent(s, re.second, 0));
-	if (g->kdone[pic->slot]) H265_CHECK(hipStreamWaitEvent(s, g->kdone[pic->slot], 0));
-	if (g->pend[pic->slot] || g->kdone[pic->slot]) H265_CHECK(hipStreamWaitEvent(s, g->ev[pic->slot], 0)); /* its copy-out */
+	if (wait_dependencies(g, pic->slot, refs, s) < 0) return -1;
 	lap("event waits");
 	H265Gpu::Timing &tm = g->tr[g->tr_next];
 	g->tr_next = (g->tr_next + 1) % 32;
 	flush_timing(g, tm);
 	H265_CHECK(hipEventRecord(tm.t0, s));
 	lap("timing");
-	if (pic->n_pu) {
-		const int grid = pic->n_pu < g->cus * 8 ? pic->n_pu : g->cus * 8;
-		hipLaunchKernelGGL(k_h265_mc, dim3(grid), dim3(64), 0, s, args);
-		H265_CHECK(hipGetLastError());
-	}
-	if (pic->n_tu && g->block_kernel) {
-		const int grid = pic->n_tu < g->cus * 8 ? pic->n_tu : g->cus * 8;
-		hipLaunchKernelGGL(k_h265_intra, dim3(grid), dim3(64), 0, s, args);
-		H265_CHECK(hipGetLastError());
-	} else if (pic->n_tu) {
-		hipLaunchKernelGGL(k_h265_ctu_index, dim3(pic->n_tu / 256 + 1), dim3(256), 0, s, args);
-		if (pic->n_pu && g->ctu_grid) {
-			if (g->waves4) hipLaunchKernelGGL(k_h265_ctu_grid<256>, dim3(nctu), dim3(256), 0, s, args);
-			else hipLaunchKernelGGL(k_h265_ctu_grid<128>, dim3(nctu), dim3(128), 0, s, args);
-		} else if (g->waves4) {
-			hipLaunchKernelGGL(k_h265_ctu_rows<256>, dim3(rows), dim3(256), 0, s, args);
-		} else {
-			hipLaunchKernelGGL(k_h265_ctu_rows<128>, dim3(rows), dim3(128), 0, s, args);
-		}
-		H265_CHECK(hipGetLastError());
-	}
+	if (launch_recon(g, pic, L, args, s) < 0) return -1;
 	lap("ctu kernels");
-	if (pic->flags & H265R_PIC_DEBLOCK) {
-		const int nv = (g->H / 4) * (g->W / 8), nh = (g->H / 8) * (g->W / 4);
-		hipLaunchKernelGGL(k_h265_deblock, dim3((nv + 255) / 256), dim3(256), 0, s, args, 0);
-		hipLaunchKernelGGL(k_h265_deblock, dim3((nh + 255) / 256), dim3(256), 0, s, args, 1);
-		H265_CHECK(hipGetLastError());
-	}
+	if (launch_deblock(g, pic, args, s) < 0) return -1;
 	lap("deblock");
-	if (pic->flags & (H265R_PIC_SAO_LUMA | H265R_PIC_SAO_CHROMA)) {
-		H265_CHECK(hipMemcpyAsync(ln.copy, h.frame, (size_t)g->W * g->H * 3 / 2, hipMemcpyDeviceToDevice, s));
-		const int nsa = (pic->pic_h + (pic->pic_h >> 1)) * (g->W >> 2); /* (4 bytes of a row per thread) */
-		hipLaunchKernelGGL(k_h265_sao, dim3((nsa + 255) / 256), dim3(256), 0, s, args);
-		H265_CHECK(hipGetLastError());
-	}
+	if (launch_sao(g, pic, ln.copy, frame, args, s) < 0) return -1;
 	lap("kernels");
 	H265_CHECK(hipEventRecord(tm.t1, s));
 	tm.pending = true;
-	H265_CHECK(hipEventRecord(a.used, s));
-	{
-		std::lock_guard<std::mutex> lk(g->amu);
-		a.recorded = true;
-		a.last = ++g->arena_clock;
-	}
-	/* this picture's kernels: what later readers of its frame wait for, and what the next writers of its
-	 * references' frames wait for */
-	hipEvent_t kd = next_event(g);
-	if (!kd) return -1;
-	H265_CHECK(hipEventRecord(kd, s));
-	for (int r = 0; r < H265R_MAX_FRAMES; ++r)
-		if ((refs >> r) & 1) {
-			auto &rd = g->readers[r];
-			auto it = std::find_if(rd.begin(), rd.end(), [k](const std::pair<int, hipEvent_t> &x) { return x.first == k; });
-			if (it != rd.end()) it->second = kd;
-			else rd.emplace_back(k, kd);
-		}
-	g->readers[pic->slot].clear();
-	g->kdone[pic->slot] = kd;
+	release.retired = true;
+	if (arena_retire(g, a, s) < 0) return -1;
+	if (record_kernels_done(g, pic->slot, refs, k) < 0) return -1;
 	lap("events");
-	/* the picture to its staging buffer, behind the kernels */
-	const int c = pic->slot;
-	const size_t bytes = (size_t)g->W * g->H * 3 / 2;
-	if (!g->stg[c]) H265_CHECK(hipHostMalloc((void **)&g->stg[c], bytes, hipHostMallocDefault));
-	if (g->kcopy_d2h && bytes % 16 == 0) {
-		void *dh = nullptr;
-		H265_CHECK(hipHostGetDevicePointer(&dh, g->stg[c], 0));
-		hipLaunchKernelGGL(k_h265_upload, dim3(256), dim3(256), 0, s, (const uint4 *)h.frame, (uint4 *)dh, bytes / 16,
-		                   (int *)nullptr, (size_t)0);
-		H265_CHECK(hipGetLastError());
-	} else {
-		H265_CHECK(hipMemcpyAsync(g->stg[c], h.frame, bytes, hipMemcpyDeviceToHost, s));
-	}
-	if (g->err_async) H265_CHECK(hipMemcpyAsync(&g->err_host[c], g->err, sizeof(int), hipMemcpyDeviceToHost, s));
-	H265_CHECK(hipEventRecord(g->ev[c], s));
+	if (copy_out(g, pic->slot, frame, s) < 0) return -1;
 	lap("copy-out");
-	g->pend[c] = true;
 	g->pictures++;
 	return 0;
 }
@@ -2249,13 +2002,10 @@ int h_sync(void *p, int slot)
 	H265_CHECK(hipEventSynchronize(g->ev[slot]));
 	{
 		/* a block hand-off that never came (bounded spin): the sticky error word, copied behind the frame on its
-		 * stream as the H.264 back end does.  M2DEC_AMD_H265_ERR_ASYNC=0 reads it here with a synchronous hipMemcpy,
-		 * whose blit runs on the null stream's hardware queue, shared with one of the picture streams: every frame
-		 * then waited for that stream's last kernel (r179 timeline: frame 0 out 3.3 ms after its copy-out) */
-		int err = 0;
-		if (g->err_async) err = __atomic_load_n(&g->err_host[slot], __ATOMIC_ACQUIRE);
-		else H265_CHECK(hipMemcpy(&err, g->err, sizeof(int), hipMemcpyDeviceToHost));
-		if (err) {
+		 * stream as the H.264 back end does.  (A synchronous hipMemcpy here ran its blit on the null stream's
+		 * hardware queue, shared with one of the picture streams: every frame then waited for that stream's last
+		 * kernel — r179 timeline: frame 0 out 3.3 ms after its copy-out) */
+		if (__atomic_load_n(&g->err_host[slot], __ATOMIC_ACQUIRE)) {
 			fprintf(stderr, "m2dec_amd: H.265 block hand-off timed out on the GPU\n");
 			return -1;
 		}
@@ -2316,15 +2066,10 @@ extern "C" int h265_hip_backend_create(h265r_backend_t *out, int device)
 	H265Gpu *g = new H265Gpu();
 	g->dev = device;
 	g->cus = prop.multiProcessorCount;
-	if (const char *e = getenv("M2DEC_AMD_H265_BLOCKS")) g->block_kernel = atoi(e) != 0;
 	if (const char *e = getenv("M2DEC_AMD_H265_CTU_GRID")) g->ctu_grid = atoi(e) != 0;
 	g->trace = getenv("M2DEC_AMD_H265_TRACE") != nullptr;
 	if (const char *e = getenv("M2DEC_AMD_H265_TRACE_MS")) g->trace_ms = atof(e);
-	if (const char *e = getenv("M2DEC_AMD_H265_UPLOAD_ZERO")) g->upload_zero = atoi(e) != 0;
 	if (const char *e = getenv("M2DEC_AMD_H265_WAVES")) g->waves4 = atoi(e) >= 4;
-	if (const char *e = getenv("M2DEC_AMD_H265_KCOPY")) g->kcopy = atoi(e) != 0;
-	if (const char *e = getenv("M2DEC_AMD_KCOPY_D2H")) g->kcopy_d2h = atoi(e) != 0;
-	if (const char *e = getenv("M2DEC_AMD_H265_ERR_ASYNC")) g->err_async = atoi(e) != 0;
 	if (const char *e = getenv("M2DEC_AMD_H265_STAGE")) g->no_stage = atoi(e) == 0;
 	{
 		const char *q = getenv("GPU_MAX_HW_QUEUES");

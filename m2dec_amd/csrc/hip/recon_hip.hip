@@ -326,11 +326,6 @@ __device__ __forceinline__ void signal_progress(int *flag, int value)
 }
 
 /* ======================================================================== k_inter */
-#ifdef M2DEC_NOINLINE
-#define M2DEC_INTER_MB_ATTR __attribute__((noinline))
-#else
-#define M2DEC_INTER_MB_ATTR
-#endif
 /* wave-private residual buffers of the inter MBs in flight in a workgroup (one MB per wave) */
 struct InterRes {
 	int r[256 + 128]; /* luma raster 16x16, then Cb / Cr 8x8 */
@@ -351,20 +346,17 @@ struct InterRes {
  * Every global load of the MB (the luma and chroma reference windows, the coefficients) is issued
  * before the first of them is waited for: one memory round trip per MB.  The samples go to the item's
  * LDS segment. */
-__device__ M2DEC_INTER_MB_ATTR void inter_mb(const int addr, const m2r_mb_t m, const m2r_inter_t &it,
+__device__ void inter_mb(const int addr, const m2r_mb_t m, const m2r_inter_t &it,
                          const m2r_slice_t *__restrict__ slices, const int16_t *__restrict__ pool, uint8_t *frames,
                          size_t fsz, int W, int H, int Wmb, uint8_t *seg, InterRes *res, const int lane_in, const int scnt = 0)
 {
 	STAMPW(scnt, 0);
 	/* the lane index through an opaque copy: every per-lane address below is then computed inside the MB
 	 * loop of the caller instead of being hoisted out of it as loop invariants, which held ~60 VGPRs across
-	 * the loop and spilled them to scratch at the 128-VGPR budget */
-#ifndef M2DEC_NO_LANE_LAUNDER
+	 * the loop and spilled them to scratch at the 128-VGPR budget (r99 and before, with the plain copy: 740 B of
+	 * scratch per lane, 63 scratch operations per MB) */
 	int lane;
 	asm volatile("v_mov_b32 %0, %1" : "=v"(lane) : "v"(lane_in));
-#else
-	const int lane = lane_in; /* r99 and before: 740 B of scratch per lane, 63 scratch operations per MB */
-#endif
 	const int mbx = addr % Wmb, mby = addr / Wmb;
 	const m2r_slice_t *sl = &slices[m.slice];
 	const int CH = H >> 1;
@@ -749,13 +741,6 @@ __device__ __forceinline__ int avail8(int b, int a)
 /* wave-level sync for the intra wavefront, which runs on ONE wave of its workgroup: lanes talk
  * through LDS only, so an LDS drain + wave barrier suffices (outstanding global prefetches are not
  * waited for) */
-#ifdef M2DEC_WSYNC_WAIT
-#define WSYNC()                                                  \
-	do {                                                         \
-		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       \
-		__builtin_amdgcn_wave_barrier();                         \
-	} while (0)
-#else
 /* a wave's LDS operations are performed in issue order, so a later ds_read of this wave sees its
  * earlier ds_writes without waiting for them: only the compiler must not move memory operations
  * across the step boundary */
@@ -764,7 +749,6 @@ __device__ __forceinline__ int avail8(int b, int a)
 		asm volatile("" ::: "memory");                           \
 		__builtin_amdgcn_wave_barrier();                         \
 	} while (0)
-#endif
 
 union MbWords {
 	m2r_mb_t m;
@@ -814,12 +798,7 @@ __device__ __forceinline__ int ipred_taps(uint32_t w, int bits, const int *nv)
  * wave(s) with do_chroma (disjoint LDS: L, R[0..255], DC, F, HV / C, R[256..383]).  q: the MB's pool
  * segment (staged in LDS).  Reference: mb_intra4x4 / intraNxN / intra16x16 / intrapcm
  * (h264.cpp:3121-3254, 4083-4127, 4407-4555, 4708-4761), residual_chroma (2374-2461). */
-#ifdef M2DEC_BODY_NOINLINE
-#define M2DEC_BODY_ATTR __attribute__((noinline))
-#else
-#define M2DEC_BODY_ATTR __forceinline__
-#endif
-__device__ M2DEC_BODY_ATTR void intra_mb_body(const m2r_mb_t &m, const int16_t *q, const int t_in, const bool do_luma,
+__device__ __forceinline__ void intra_mb_body(const m2r_mb_t &m, const int16_t *q, const int t_in, const bool do_luma,
                                               const bool do_chroma, IntraLDS *ctx, const IntraTables *tabs)
 {
 	/* the lane index laundered per call: inside intra_row's MB loop every lane-dependent address
@@ -1173,12 +1152,7 @@ __device__ M2DEC_BODY_ATTR void intra_mb_body(const m2r_mb_t &m, const int16_t *
 	}
 }
 
-#ifdef M2DEC_INTRA_ROW_INLINE
-#define M2DEC_INTRA_ROW_ATTR __attribute__((always_inline))
-#else
-#define M2DEC_INTRA_ROW_ATTR __attribute__((noinline))
-#endif
-__device__ M2DEC_INTRA_ROW_ATTR void intra_row(const int y, const int t, const int part, lds_u8 *lds, const int wave,
+__device__ __attribute__((noinline)) void intra_row(const int y, const int t, const int part, lds_u8 *lds, const int wave,
                           const m2r_mb_t *__restrict__ mbs, const int16_t *__restrict__ pool, uint8_t *cur, int W, int H, int Wmb,
                           uint8_t *hbi, const uint32_t tag, int *err)
 {
@@ -1494,14 +1468,9 @@ __device__ __attribute__((noinline)) void intra_mb_wg(const int x, const int y, 
  * raises its done flag, which the picture's deblocking loader streams on.  The grid is kept small (a
  * fraction of the CUs) so that spinning items can never keep the work they wait for off the device.
  */
-/* (M2DEC_INTER_WORKER_NOINLINE: an out-of-line inter worker — r71: its MB loop spills more, 101 scratch
- * operations per MB and wave instead of 63, so it stays inlined) */
-#ifdef M2DEC_INTER_WORKER_NOINLINE
-#define M2DEC_INTER_WORKER_ATTR __attribute__((noinline))
-#else
-#define M2DEC_INTER_WORKER_ATTR
-#endif
-__device__ M2DEC_INTER_WORKER_ATTR void inter_worker(const PictureArgs &a, const SlotSeq &ss, uint8_t *smem)
+/* (an out-of-line inter worker — r71: its MB loop spills more, 101 scratch operations per MB and wave instead
+ * of 63, so it is left to the inliner) */
+__device__ void inter_worker(const PictureArgs &a, const SlotSeq &ss, uint8_t *smem)
 {
 	__shared__ int s_item, s_rmin, s_rmax, s_cmax, s_intra, s_rec;
 	/* the item's MB records and the motion records of its inter MBs, staged once per item */
@@ -1541,11 +1510,9 @@ __device__ M2DEC_INTER_WORKER_ATTR void inter_worker(const PictureArgs &a, const
 		__syncthreads();
 		const int item = __builtin_amdgcn_readfirstlane(s_item);
 		if (item >= nitems) break;
-#ifndef M2DEC_NO_ITEM_LAUNDER
 		/* (as in inter_mb: per-lane values re-derived per item instead of held across the item loop) */
 		int t = threadIdx.x;
 		asm volatile("" : "+v"(t));
-#endif
 		const int y = item / nseg, seg = item % nseg, x0 = seg * 8, x1 = min(x0 + 8, Wmb);
 		STAMPI(96 + (blockIdx.x & 63), 0, nst_dbg & 255, item);
 		/* ---- the item's records into LDS: MB records, then the motion records they point at */
@@ -1606,8 +1573,7 @@ __device__ M2DEC_INTER_WORKER_ATTR void inter_worker(const PictureArgs &a, const
 		const int rec_bits = __builtin_amdgcn_readfirstlane(s_rec);
 		if (rmax_u >= 0 && wave0) {
 			unsigned spins = 0;
-#ifndef M2DEC_NO_REFWAIT
-			if (rmax_u >= 0) {
+			{
 				/* rows rmin .. rmax final up to the reach: their own stores and the next row's (rows 13..15)
 				 * done.  Columns are whole 128-byte lines (8 MBs) when the stride allows, else whole rows:
 				 * a line cached while partly unfinal could outlive the acquire below */
@@ -1636,7 +1602,6 @@ __device__ M2DEC_INTER_WORKER_ATTR void inter_worker(const PictureArgs &a, const
 					}
 				}
 			}
-#endif
 			/* ALWAYS acquire, even when every flag was already set: this XCD's L2 may hold lines of
 			 * rows 13..15 that the row's own deblock workgroup loaded before the row below filtered
 			 * and rewrote them from another XCD */
@@ -1809,9 +1774,6 @@ __device__ uint32_t bs_of(const m2r_mb_t *__restrict__ mbs, const m2r_inter_t *_
 	return str;
 }
 
-#ifdef M2DEC_DBK_NOINLINE
-__attribute__((noinline))
-#endif
 __device__ void deblock_pair(const int yA, const bool hasB, uint8_t *smem, const m2r_deblock_t *__restrict__ dbk, uint8_t *cur,
                              int W, int H, int Wmb, int Hmb, uint8_t *hbd, int *progress, int *err,
                              unsigned long long *rowflag, int seq, const int *segdone,
@@ -1827,7 +1789,6 @@ __device__ void deblock_pair(const int yA, const bool hasB, uint8_t *smem, const
 	m2r_deblock_t *rA = rT + Wmb;            /* [Wmb] row A */
 	m2r_deblock_t *rB = rA + Wmb;            /* [Wmb] row B */
 	int *flags = (int *)(rB + Wmb);          /* [0] MBs loaded, [1] row A MBs filtered, [2] MBs stored, [3] row B MBs filtered */
-	uint8_t *dummy = (uint8_t *)(flags + 4);  /* [64] per-lane sink for the filter's masked-off samples */
 	uint8_t *chroma = cur + (size_t)W * H;
 	const int yB = yA + 1;
 	const bool lastA = !hasB;                /* row A is the picture's last row */
@@ -1975,7 +1936,6 @@ __device__ void deblock_pair(const int yA, const bool hasB, uint8_t *smem, const
 		const int cl = t & 7;                 /* chroma line (row for dir 0, column for dir 1) */
 		const int seg_l = (t & 15) >> 2, seg_c = cl >> 1;
 		const int seg = luma ? seg_l : seg_c;
-		uint8_t *const sink = dummy + t;
 		/* bit offset of v[i] in its dword for the vertical edges, by i & 3: luma byte i & 3; chroma (Cb / Cr
 		 * interleaved) byte 2 (i & 1) + comp */
 		const int vsh[4] = {luma ? 0 : 8 * comp, luma ? 8 : 16 + 8 * comp, luma ? 16 : 8 * comp, luma ? 24 : 16 + 8 * comp};
@@ -2023,10 +1983,9 @@ __device__ void deblock_pair(const int yA, const bool hasB, uint8_t *smem, const
 						cst = S;
 					}
 #define DBK_ADDR(j) (dir == 0 ? lb + ((c0 + (j) * cst) & M) : lb + (j) * cst)
-					/* branch-free sample access: a masked-off sample goes to the lane's dummy byte (an
+					/* branch-free sample access: every lane reads all 20 samples, in bounds, and uses its own (an
 					 * exec-masked load/store per sample would cost a branch each) */
 					int v[20];
-#ifndef M2DEC_DBK_BYTE_V
 					if (dir == 0) {
 						/* vertical edges: the line's 20 bytes from 4 left of the MB are 5 aligned dwords of the
 						 * ring line (a chroma line's samples are every other byte of the first 4: v[2..5] /
@@ -2036,24 +1995,13 @@ __device__ void deblock_pair(const int yA, const bool hasB, uint8_t *smem, const
 						for (int k = 0; k < 5; ++k) dw[k] = *(const uint32_t *)(lb + ((base - 4 + 4 * k) & M));
 #pragma unroll
 						for (int i = 0; i < 20; ++i) v[i] = (int)__builtin_amdgcn_ubfe(dw[i >> 2], (uint32_t)vsh[i & 3], 8);
-					} else
-#endif
-#ifndef M2DEC_DBK_BYTE_H
-					if (dir == 1) {
+					} else {
 						/* horizontal edges: one byte per line at a fixed stride, so every load is an immediate
 						 * offset from one of two per-lane bases (a chroma lane's v[2..5] / v[10..13] are its
 						 * samples 0..3 / 4..7; its other v[] read in-bounds bytes it never uses) */
 						const uint8_t *const blo = luma ? lb : lb - 2 * S, *const bhi = luma ? lb : lb - 6 * S;
 #pragma unroll
 						for (int i = 0; i < 20; ++i) v[i] = (i < 6 ? blo : bhi)[i * S];
-					} else
-#endif
-#pragma unroll
-					for (int i = 0; i < 20; ++i) {
-						const int ci = (i < 6) ? i - 2 : i - 6; /* chroma sample index for v[i] */
-						const bool cv = (i >= 2 && i <= 5) || (i >= 10 && i <= 13);
-						const bool ok = active && (luma || cv);
-						v[i] = *(ok ? DBK_ADDR(luma ? i : ci) : sink);
 					}
 #pragma unroll
 					for (int e = 0; e < 4; ++e) {
@@ -2103,7 +2051,6 @@ __device__ void deblock_pair(const int yA, const bool hasB, uint8_t *smem, const
 					/* write back; at x == 0 the 4 columns left of the MB wrap onto a slot the loader may
 					 * be filling, and edge 0 is off there anyway */
 					const int i0 = (dir == 0 && x == 0) ? 4 : 1;
-#ifndef M2DEC_DBK_BYTE_V
 					if (dir == 0) {
 						/* luma lines back as dwords (bytes 0 and 19 are p3 / q3, never changed); chroma lanes
 						 * share dwords between Cb and Cr, so their 8 samples stay byte stores */
@@ -2121,10 +2068,7 @@ __device__ void deblock_pair(const int yA, const bool hasB, uint8_t *smem, const
 								if (i >= i0) *DBK_ADDR(ci) = (uint8_t)v[i];
 							}
 						}
-					} else
-#endif
-#ifndef M2DEC_DBK_BYTE_H
-					if (dir == 1) {
+					} else {
 						if (luma) {
 #pragma unroll
 							for (int i = 1; i < 19; ++i) lb[i * S] = (uint8_t)v[i];
@@ -2135,14 +2079,6 @@ __device__ void deblock_pair(const int yA, const bool hasB, uint8_t *smem, const
 								lb[((i < 6) ? i - 2 : i - 6) * S] = (uint8_t)v[i];
 							}
 						}
-					} else
-#endif
-#pragma unroll
-					for (int i = 1; i < 19; ++i) {
-						const int ci = (i < 6) ? i - 2 : i - 6;
-						const bool cv = (i >= 2 && i <= 5) || (i >= 10 && i <= 13);
-						const bool ok = i >= i0 && active && (luma || cv);
-						*(ok ? DBK_ADDR(luma ? i : ci) : sink) = (uint8_t)v[i];
 					}
 #undef DBK_ADDR
 					/* the next direction's reads are this wave's later LDS operations: performed in order */
@@ -2444,6 +2380,8 @@ __global__ __launch_bounds__(256, M2DEC_MIN_BLOCKS) void k_picture(const Picture
 size_t m2r_deblock_lds_bytes(int W, int Wmb)
 {
 	(void)W;
+	/* (the last 64 bytes are spare — once the filter's sink for masked-off samples —, kept so that the workgroup's
+	 * LDS size is the one the kernels were measured with) */
 	const size_t dbk = (size_t)54 * DBK_RW + 3 * (size_t)Wmb * sizeof(m2r_deblock_t) + 16 + 64;
 	const size_t intra = 4 * sizeof(IntraLDS) + sizeof(IntraTables);
 	const size_t worker = sizeof(IntraLDS) + sizeof(IntraTables) + 24 * SEG_ROW + 4 * sizeof(InterRes);

@@ -59,12 +59,16 @@ for step in "$@"; do
       rc=$?; find $O/prof_$TAG -name "*kernel_stats*" ;;
     h265ab)
       IFS=',' read -r rounds var va vb <<< "$arg"
-      for ((i = 0; i < rounds; i++)); do
+      rc=0
+      for ((i = 0; i < rounds && rc == 0; i++)); do
         for v in $va $vb; do
-          echo "$var=$v $(env $var=$v timeout -k 10 300 python tools/h265_bench.py 10)" >> $O/h265ab_$TAG.txt || exit 1
+          # (a failed run ends the step: the exit status of a command substitution inside echo's argument is lost)
+          out=$(env $var=$v timeout -k 10 300 python tools/h265_bench.py 10); rc=$?
+          [ $rc -ne 0 ] && break
+          echo "$var=$v $out" >> $O/h265ab_$TAG.txt
         done
       done
-      rc=$?; python3 tools/h265_ab_summary.py $O/h265ab_$TAG.txt ;;
+      [ $rc -eq 0 ] && python3 tools/h265_ab_summary.py $O/h265ab_$TAG.txt ;;
     h265tl)
       IFS=',' read -r n st <<< "$arg"
       timeout -k 10 400 bash tools/h265_timeline.sh $TAG ${n:-4} ${st:-c_h265_1080p_s1}; rc=$? ;;
