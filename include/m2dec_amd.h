@@ -356,6 +356,10 @@ int m2dec_amd_h265_parser_hits(long *out, int n, int reset);
 uint64_t m2dec_amd_h265_cabac_bins(const void *ctx);
 /* The gfx950 H.265 reconstruction back end (m2dec_amd/csrc/hip/h265_hip.hip). */
 int m2dec_amd_h265_hip_backend_create(h265r_backend_t *out, int device);
+/* Copy the caller's frames (set_frames) as they are now into its device frames, which start zeroed and are never
+ * read from the caller otherwise; call with no picture in flight.  For callers whose frames already hold pictures
+ * (tests/_h265_records.py: every back end starts from the same seeded bytes).  -1 on error. */
+int m2dec_amd_h265_hip_upload_frames(const h265r_backend_t *be);
 /* Its kernel time (HIP events over the intra / deblocking / SAO launches of a picture, all but the last
  * picture submitted), and the SURVEY.md §8d bytes of the pictures so far: R_pic (records uploaded) and
  * F_write (1.5 W H each).  reset restarts the counts. */

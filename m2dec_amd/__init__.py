@@ -795,6 +795,15 @@ class H265HipBackend:
                                     ctypes.byref(fb), int(reset))
         return {"kernel_us": us.value, "pictures": n.value, "record_bytes": rb.value, "frame_bytes": fb.value}
 
+    def upload_frames(self) -> None:
+        """The caller's frames (set_frames) as they are now into the device frames (m2dec_amd_h265_hip_upload_frames):
+        the back end otherwise starts from zeroed frames and never reads the caller's."""
+        L = lib()
+        L.m2dec_amd_h265_hip_upload_frames.argtypes = [ctypes.POINTER(Backend265)]
+        L.m2dec_amd_h265_hip_upload_frames.restype = ctypes.c_int
+        if L.m2dec_amd_h265_hip_upload_frames(ctypes.byref(self.be)) < 0:
+            raise RuntimeError("m2dec_amd: H.265 frame upload failed")
+
     def close(self) -> None:
         if self.be.destroy:
             ctypes.CFUNCTYPE(None, ctypes.c_void_p)(self.be.destroy)(self.be.self)

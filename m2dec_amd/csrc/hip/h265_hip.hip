@@ -2107,6 +2107,28 @@ extern "C" int h265_hip_backend_create(h265r_backend_t *out, int device)
 
 extern "C" int m2dec_amd_h265_hip_backend_create(h265r_backend_t *out, int device) { return h265_hip_backend_create(out, device); }
 
+/* The caller's frames as they are now into the device frames (after set_frames, with no picture in flight).  The
+ * back end keeps every frame in device memory, zeroed when allocated, and never reads the caller's: a back-end user
+ * whose frames already hold pictures (references decoded elsewhere; the record-level tests' seeded fill) calls this
+ * so that a prediction from a slot no picture was submitted into, and the bytes of a frame no block writes, are the
+ * caller's.  Not on the decode path. */
+extern "C" int m2dec_amd_h265_hip_upload_frames(const h265r_backend_t *be)
+{
+	if (!be || !be->self || be->submit != h_submit) return -1;
+	H265Gpu *g = (H265Gpu *)be->self;
+	if (!g->frames) return -1;
+	H265_CHECK(hipSetDevice(g->dev));
+	if (sync_all(g) < 0) return -1;
+	const size_t ls = (size_t)g->W * g->H;
+	for (int i = 0; i < g->n; ++i) {
+		uint8_t *f = g->frames + (size_t)i * g->fsz;
+		if (!g->caller[i].luma || !g->caller[i].chroma) return -1;
+		H265_CHECK(hipMemcpy(f, g->caller[i].luma, ls, hipMemcpyHostToDevice));
+		H265_CHECK(hipMemcpy(f + ls, g->caller[i].chroma, ls / 2, hipMemcpyHostToDevice));
+	}
+	return 0;
+}
+
 /* kernel time (HIP events per picture on its stream: pictures on different streams overlap, so this is the
  * sum of the pictures' kernel latencies), pictures, and the §8d algorithmic bytes of the pictures so far: R_pic
  * (records uploaded) and F_write (1.5 W H each); reset zeroes them */

@@ -27,6 +27,7 @@
  * every DC-only term the reference's byte-wise SWAR add would corrupt (|dc| > 255) is counted:
  * golden streams must have none.
  */
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -621,4 +622,34 @@ int h265_oracle_backend_create(h265r_backend_t *out)
 	out->destroy = o_destroy;
 	out->stage = NULL;
 	return 0;
+}
+
+/* ------------------------------------------------------------------ record layout (test hook)
+ * sizeof and offsetof of the h265r_* records as this compiler lays them out, in the order of LAYOUT in
+ * tests/_h265_records.py, whose ctypes mirrors are checked against it; returns the number of values */
+int h265_oracle_layout(int32_t *out, int max)
+{
+#define SZ(t) (int32_t)sizeof(t)
+#define OF(t, f) (int32_t)offsetof(t, f)
+	const int32_t v[] = {
+		SZ(h265r_tu_t), OF(h265r_tu_t, x), OF(h265r_tu_t, y), OF(h265r_tu_t, log2), OF(h265r_tu_t, plane), OF(h265r_tu_t, mode),
+		OF(h265r_tu_t, flags), OF(h265r_tu_t, avail_top), OF(h265r_tu_t, avail_left), OF(h265r_tu_t, res), OF(h265r_tu_t, strong),
+		OF(h265r_tu_t, pad), OF(h265r_tu_t, coef),
+		SZ(h265r_pu_t), OF(h265r_pu_t, x), OF(h265r_pu_t, y), OF(h265r_pu_t, w), OF(h265r_pu_t, h), OF(h265r_pu_t, ref),
+		OF(h265r_pu_t, mv),
+		SZ(h265r_sao_t), OF(h265r_sao_t, type), OF(h265r_sao_t, band), OF(h265r_sao_t, eo), OF(h265r_sao_t, pad), OF(h265r_sao_t, off),
+		SZ(h265r_picture_t), OF(h265r_picture_t, width), OF(h265r_picture_t, height), OF(h265r_picture_t, pic_w),
+		OF(h265r_picture_t, pic_h), OF(h265r_picture_t, ctb_log2), OF(h265r_picture_t, slot), OF(h265r_picture_t, n_tu),
+		OF(h265r_picture_t, n_coef), OF(h265r_picture_t, flags), OF(h265r_picture_t, beta_offset), OF(h265r_picture_t, tc_offset),
+		OF(h265r_picture_t, cb_qp_offset), OF(h265r_picture_t, cr_qp_offset), OF(h265r_picture_t, tu), OF(h265r_picture_t, coef),
+		OF(h265r_picture_t, map), OF(h265r_picture_t, bs_v), OF(h265r_picture_t, bs_h), OF(h265r_picture_t, sao),
+		OF(h265r_picture_t, n_pu), OF(h265r_picture_t, pu),
+		SZ(h265r_backend_t), OF(h265r_backend_t, self), OF(h265r_backend_t, set_frames), OF(h265r_backend_t, submit),
+		OF(h265r_backend_t, sync_frame), OF(h265r_backend_t, destroy), OF(h265r_backend_t, stage),
+	};
+#undef SZ
+#undef OF
+	const int n = (int)(sizeof(v) / sizeof(v[0]));
+	for (int i = 0; i < n && i < max; ++i) out[i] = v[i];
+	return n;
 }
