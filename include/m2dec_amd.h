@@ -52,11 +52,12 @@ typedef struct {
 /* ABI revision of the structs in this header and m2d_recon.h.  3: m2r_backend_t gained `bind` (decode
  * ahead) and m2dec_amd_stats_t grew to its current size; 4: m2r_backend_t gained `flush` (several
  * pictures per launch); 5: `ready`; 6: `records_busy` (M2R_PIC_EXTERNAL: uploads from the parser's own
- * pinned records).  A caller compiled against another revision
+ * pinned records); 7: m2dec_amd_devout_t gained the trailing scale / element-type fields (read only when
+ * `size` covers them: the revision-6 struct still converts unscaled).  A caller compiled against another revision
  * checks m2dec_amd_abi_version() before passing either struct; m2dec_amd_h264_set_backend2 accepts an
  * older (smaller) m2r_backend_t by size, and m2dec_amd_stats_size() is the size every stats pointer
  * must have room for. */
-#define M2DEC_AMD_ABI_VERSION 6
+#define M2DEC_AMD_ABI_VERSION 7
 int m2dec_amd_abi_version(void);
 size_t m2dec_amd_stats_size(void);
 /* 0 if the host CPU lacks the x86-64-v3 features the host library is built for (decoder inits then
@@ -116,24 +117,66 @@ int m2dec_amd_decode_stream2(const uint8_t *data, size_t len, const m2r_backend_
  * RGB: H x W x 3 interleaved; RGBP: 3 x H x W planar.  Crops and the cropped size must be even (-1 otherwise). */
 enum { M2DEC_AMD_OUT_NV12 = 0, M2DEC_AMD_OUT_RGB = 1, M2DEC_AMD_OUT_RGBP = 2 };
 enum { M2DEC_AMD_BT709 = 0, M2DEC_AMD_BT601 = 1 };
+/* ---- scaled and normalised output (RGB / RGBP only).  The frame is converted as above at the
+ * cropped size cw x ch, the 8-bit RGB resampled to out_width x out_height, and the result stored as uint8 or as
+ * normalised float16 / float32.  Integer arithmetic throughout, stated once (host: frame_out.c, gfx950:
+ * frame_out.hip k_frame_scale, bit-identical):
+ *  Tap tables (m2dec_amd_scale_taps), per axis with source length S and output length On: output o reads the
+ *   source run [start[o], start[o] + count[o]) with 14-bit weights >= 0 that sum to ONE = 16384.  From the taps'
+ *   integer overlaps v_k with total T: w_k = Rnd(c_k + v_k) - Rnd(c_k), c_k the sum of the earlier overlaps,
+ *   Rnd(c) = (2 c ONE + T) / (2 T) rounded down, all in 64-bit integers.
+ *    BILINEAR (half-pixel centres, no antialias: torch interpolate align_corners=False, cv2.INTER_LINEAR):
+ *     num = (2 o + 1) S - On, den = 2 On, i0 = floor(num / den), rem = num - i0 den; taps (i0, den - rem) and
+ *     (i0 + 1, rem), T = den.
+ *    AREA (the exact box filter, cv2.INTER_AREA; legal for upscaling): in units of 1 / On output o covers
+ *     [o S, (o + 1) S) and source i covers [i On, (i + 1) On); the taps are every i with a positive overlap, v_i
+ *     that overlap, T = S.
+ *   Indices are clamped to [0, S - 1] and taps on one index merged (overlaps added) before the rounding; taps of
+ *   weight 0 at either end are dropped.  More than M2DEC_AMD_SCALE_MAX_TAPS taps for any output: refused.
+ *  Horizontal pass, then vertical pass (the order is part of the definition), per channel:
+ *   h = (sum wx v + 32) >> 6 (<= 65280: uint16), q = clip255((sum wy h + (1 << 21)) >> 22) (the sum < 2^32).
+ *   An output size equal to the cropped size returns the conversion's bytes.
+ *  Element: U8 stores q; F32 stores fmaf((float)q, a_c, b_c) with a_c = (float)(1.0 / (255.0 std_c)) and
+ *   b_c = (float)(-mean_c / std_c) computed in double (mean 0, std 1: q / 255); F16 stores that float rounded to
+ *   nearest even.  RGB: out_height x out_width x 3 elements; RGBP: 3 x out_height x out_width.
+ * Refused (-1 / 0 bytes, nothing written, nothing rounded into validity): NV12 with a scale or a non-U8 dtype;
+ * out_width or out_height < 1 unless both are 0 (= unscaled); an unknown filter or dtype; with F16 / F32 a
+ * std <= 0 or non-finite, or a non-finite mean; more than 32 taps on an axis; a device destination not aligned to
+ * the element size. */
+enum { M2DEC_AMD_SCALE_BILINEAR = 0, M2DEC_AMD_SCALE_AREA = 1 };
+enum { M2DEC_AMD_DT_U8 = 0, M2DEC_AMD_DT_F16 = 1, M2DEC_AMD_DT_F32 = 2 };
+#define M2DEC_AMD_SCALE_ONE 16384
+#define M2DEC_AMD_SCALE_MAX_TAPS 32
 typedef struct {
 	size_t size;          /* sizeof of the caller's struct */
 	int format, matrix, full_range;
 	/* called on the thread that called the driver, once per output frame in output order, before the frame is
-	 * written: the device address (on `device`) for frame `index` of width x height (cropped), `bytes` long;
-	 * NULL ends the decode with an error */
+	 * written: the device address (on `device`) for frame `index` of width x height (the output size: cropped,
+	 * or out_width x out_height), `bytes` long; NULL ends the decode with an error */
 	void *(*frame_dst)(void *arg, int index, int width, int height, size_t bytes);
 	void *arg;
+	/* revision 7, read only when `size` covers them (a shorter struct: unscaled U8) */
+	int out_width, out_height; /* 0 / 0: the cropped size */
+	int filter, dtype;
+	float mean[3], std[3];     /* per channel (R, G, B), in units of the full scale 255; F16 / F32 only */
 } m2dec_amd_devout_t;
 /* bytes of one cropped width x height frame in `format` (0 for a bad format or an odd / non-positive size) */
 size_t m2dec_amd_frame_out_bytes(int format, int width, int height);
-/* The conversion over a host frame into out (m2dec_amd_frame_out_bytes long); only size, format, matrix and
- * full_range of cfg are read.  0, or -1 (nothing written) for a bad cfg, an odd crop or an empty cropped frame. */
+/* bytes of one output frame of a crop_w x crop_h cropped picture under cfg, its size into out_w / out_h (either may
+ * be NULL); 0 when cfg is refused for that picture (see above) */
+size_t m2dec_amd_frame_out_bytes2(const m2dec_amd_devout_t *cfg, int crop_w, int crop_h, int *out_w, int *out_h);
+/* The tap table of one axis: start[On], count[On] and weights[On][M2DEC_AMD_SCALE_MAX_TAPS] (a row's unused tail
+ * is 0).  0, or -1 (nothing written) for a bad argument (S or On outside 1 .. 16384, an unknown filter, a NULL
+ * pointer) or an output that needs more than 32 taps. */
+int m2dec_amd_scale_taps(int S, int On, int filter, int16_t *start, int16_t *count, uint16_t *weights);
+/* The conversion over a host frame into out (m2dec_amd_frame_out_bytes2 long); frame_dst and arg of cfg are not
+ * read.  0, or -1 (nothing written) for a bad cfg, an odd crop or an empty cropped frame. */
 int m2dec_amd_frame_convert_host(const m2d_frame_t *f, const m2dec_amd_devout_t *cfg, uint8_t *out);
 /* Kernel parity entry: the host planes (luma width x height, stride width; chroma width x height / 2) are uploaded
- * in the back end's picture layout, k_frame_out writes the cropped frame to (device buffer) + out_offset
- * (0 .. 15: unaligned destinations), and the device buffer's bytes [out_offset - guard, out_offset + bytes + guard)
- * with guard = 64 come back into out_host (bytes + 128 long; the guards hold 0xA5 when nothing wrote them). */
+ * in the back end's picture layout, k_frame_out (k_frame_scale for a scaled or float cfg) writes the output frame
+ * to (device buffer) + out_offset (0 .. 15: unaligned destinations; a multiple of the element size), and the device
+ * buffer's bytes [out_offset - guard, out_offset + bytes + guard) with guard = 64 come back into out_host
+ * (bytes + 128 long; the guards hold 0xA5 when nothing wrote them). */
 int m2dec_amd_hip_frame_convert(int device, const uint8_t *luma, const uint8_t *chroma, int width, int height,
                                 const int16_t crop[4], const m2dec_amd_devout_t *cfg, uint8_t *out_host,
                                 size_t out_offset);
@@ -154,12 +197,13 @@ int m2dec_amd_hip_backend_create(m2r_backend_t *out, int device);
 /* Device-output mode of a HIP back end (set before its first set_frames; 0 / -1): the per-slot staging buffers
  * are device memory holding the raw NV12 picture, sync_frame neither waits for pixels nor writes the caller's
  * frames (which may then be small placeholders), and the caller takes each frame with emit:
- *   emit(be, slot, crop, cfg, dst_dev): k_frame_out from the slot's staging to dst_dev, enqueued behind the
+ *   emit(be, slot, crop, cfg, dst_dev): k_frame_out (or k_frame_scale, its tap tables built and uploaded at the
+ *     back end's first emit and kept) from the slot's staging to dst_dev, enqueued behind the
  *     picture's copy; call it after the frame left get / peek_decoded_frame and before the next decode_picture
  *     (the lifetime get_decoded_frame gives a host frame).  The staging is not reused before the conversion read it.
  *   finish(be): waits for everything emitted (then visible to every stream of the process) and checks the
  *     kernels' error word (-1: a wavefront hand-off failed); call it before the frames are used and before destroy.
- *   frame_out_timing (process-wide): HIP-event time of the k_frame_out launches of finished back ends' emits and
+ *   frame_out_timing (process-wide): HIP-event time of the k_frame_out / k_frame_scale launches of finished back ends' emits and
  *     their count since the last reset (M2DEC_AMD_TIMING=0: not timed). */
 int m2dec_amd_hip_backend_set_device_output(const m2r_backend_t *be, int on);
 int m2dec_amd_hip_backend_emit(const m2r_backend_t *be, int slot, const int16_t crop[4], const m2dec_amd_devout_t *cfg,

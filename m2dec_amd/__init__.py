@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("M2DEC_AMD_LIB") or os.path.join(_HERE, "lib", "libm2d
 
 __all__ = [
     "LIB_PATH", "Frame", "Backend", "Stats", "HipTiming", "lib", "hip_available", "HipBackend",
-    "decode_stream", "decode_stream_md5", "decode_streams", "decode_m2v", "m2v_last_checks", "decode_table_frames", "frame_md5", "frame_nv12", "DevOut", "DeviceFrames", "decode_to_device", "frame_convert_host", "hip_frame_convert", "frame_out_timing", "H264Decoder", "Trace", "HipReplay", "TracePic",
+    "decode_stream", "decode_stream_md5", "decode_streams", "decode_m2v", "m2v_last_checks", "decode_table_frames", "frame_md5", "frame_nv12", "DevOut", "DeviceFrames", "decode_to_device", "frame_convert_host", "hip_frame_convert", "scale_taps", "frame_out_timing", "H264Decoder", "Trace", "HipReplay", "TracePic",
 ]
 
 
@@ -95,13 +95,20 @@ FRAME_DST = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, cty
 
 
 class DevOut(ctypes.Structure):
-    """m2dec_amd_devout_t (include/m2dec_amd.h): output format, matrix, range and the destination callback."""
+    """m2dec_amd_devout_t (include/m2dec_amd.h): output format, matrix, range, the destination callback, and the
+    scaled / normalised output's size, filter, element type, mean and std."""
     _fields_ = [("size", ctypes.c_size_t), ("format", ctypes.c_int), ("matrix", ctypes.c_int),
-                ("full_range", ctypes.c_int), ("frame_dst", FRAME_DST), ("arg", ctypes.c_void_p)]
+                ("full_range", ctypes.c_int), ("frame_dst", FRAME_DST), ("arg", ctypes.c_void_p),
+                ("out_width", ctypes.c_int), ("out_height", ctypes.c_int), ("filter", ctypes.c_int),
+                ("dtype", ctypes.c_int), ("mean", ctypes.c_float * 3), ("std", ctypes.c_float * 3)]
 
 
 OUT_FORMATS = {"nv12": 0, "rgb": 1, "rgbp": 2}
 OUT_MATRICES = {"bt709": 0, "bt601": 1}
+OUT_FILTERS = {"bilinear": 0, "area": 1}
+OUT_DTYPES = {"u8": 0, "f16": 1, "f32": 2}
+_DTYPE_NUMPY = {"u8": ("uint8", "|u1", 1), "f16": ("float16", "<f2", 2), "f32": ("float32", "<f4", 4)}
+SCALE_MAX_TAPS = 32
 
 _lib = None
 
@@ -199,6 +206,10 @@ def lib() -> ctypes.CDLL:
         L.m2dec_amd_hip_replay_destroy.restype = None
         L.m2dec_amd_frame_out_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
         L.m2dec_amd_frame_out_bytes.restype = ctypes.c_size_t
+        L.m2dec_amd_frame_out_bytes2.argtypes = [ctypes.POINTER(DevOut), ctypes.c_int, ctypes.c_int, ip, ip]
+        L.m2dec_amd_frame_out_bytes2.restype = ctypes.c_size_t
+        L.m2dec_amd_scale_taps.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]
+        L.m2dec_amd_scale_taps.restype = ctypes.c_int
         L.m2dec_amd_frame_convert_host.argtypes = [ctypes.POINTER(Frame), ctypes.POINTER(DevOut), vp]
         L.m2dec_amd_frame_convert_host.restype = ctypes.c_int
         L.m2dec_amd_hip_frame_convert.argtypes = [ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int,
@@ -352,32 +363,93 @@ def decode_stream_md5(data: bytes, device: int = 0, dpb: int = -1, stats: Option
     return [raw[35 * i:35 * i + 32].decode() for i in range(min(n, cap))]
 
 
-def _devout(fmt: str, matrix: str, full_range: bool) -> DevOut:
+def _devout(fmt: str, matrix: str, full_range: bool, size=None, filter: str = "bilinear", dtype: str = "u8",
+            mean=(0, 0, 0), std=(1, 1, 1)) -> DevOut:
+    """The config of the keyword arguments; ValueError for everything that can be refused without the picture."""
+    import math
     if fmt not in OUT_FORMATS or matrix not in OUT_MATRICES:
         raise ValueError(f"m2dec_amd: format {fmt!r} (nv12 / rgb / rgbp) or matrix {matrix!r} (bt709 / bt601) unknown")
+    if filter not in OUT_FILTERS or dtype not in OUT_DTYPES:
+        raise ValueError(f"m2dec_amd: filter {filter!r} (bilinear / area) or dtype {dtype!r} (u8 / f16 / f32) unknown")
+    oh = ow = 0
+    if size is not None:
+        try:
+            oh, ow = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError(f"m2dec_amd: size {size!r} is not (height, width)") from None
+        if oh < 1 or ow < 1 or oh > 16384 or ow > 16384:
+            raise ValueError(f"m2dec_amd: size {size!r} outside 1 .. 16384")
+    if fmt == "nv12" and (size is not None or dtype != "u8"):
+        raise ValueError("m2dec_amd: nv12 output is neither scaled nor converted to float")
+    try:
+        mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+    except (TypeError, ValueError):
+        raise ValueError("m2dec_amd: mean and std are three numbers each") from None
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("m2dec_amd: mean and std are three numbers each")
+    if dtype != "u8":
+        cf = ctypes.c_float
+        if not all(math.isfinite(cf(m).value) for m in mean) or not all(math.isfinite(cf(v).value) and cf(v).value > 0 for v in std):
+            raise ValueError(f"m2dec_amd: mean {mean} must be finite and std {std} finite and > 0")
     return DevOut(size=ctypes.sizeof(DevOut), format=OUT_FORMATS[fmt], matrix=OUT_MATRICES[matrix],
-                  full_range=1 if full_range else 0)
+                  full_range=1 if full_range else 0, out_width=ow, out_height=oh, filter=OUT_FILTERS[filter],
+                  dtype=OUT_DTYPES[dtype], mean=(ctypes.c_float * 3)(*mean), std=(ctypes.c_float * 3)(*std))
 
 
-def frame_convert_host(f: Frame, fmt: str = "rgb", matrix: str = "bt709", full_range: bool = False) -> bytes:
+def _out_bytes(cfg: DevOut, cw: int, ch: int):
+    """(bytes, out_w, out_h) of a cw x ch cropped picture under cfg; ValueError when the library refuses it."""
+    ow, oh = ctypes.c_int(), ctypes.c_int()
+    n = lib().m2dec_amd_frame_out_bytes2(ctypes.byref(cfg), cw, ch, ctypes.byref(ow), ctypes.byref(oh))
+    if not n:
+        raise ValueError(f"m2dec_amd: a {cw} x {ch} picture is refused under this output config (odd or empty crop, "
+                         f"or more than {SCALE_MAX_TAPS} taps per output pixel)")
+    return n, ow.value, oh.value
+
+
+def scale_taps(S: int, On: int, filter: str = "bilinear"):
+    """The tap table of one axis (m2dec_amd_scale_taps): numpy (start[On], count[On], weights[On, 32]).  ValueError
+    for a bad argument or more than 32 taps."""
+    import numpy as np
+    if filter not in OUT_FILTERS:
+        raise ValueError(f"m2dec_amd: filter {filter!r} (bilinear / area) unknown")
+    n = max(1, min(int(On), 16384))
+    start, count = np.zeros(n, np.int16), np.zeros(n, np.int16)
+    weights = np.zeros((n, SCALE_MAX_TAPS), np.uint16)
+    if lib().m2dec_amd_scale_taps(int(S), int(On), OUT_FILTERS[filter], start.ctypes.data, count.ctypes.data,
+                                  weights.ctypes.data) < 0:
+        raise ValueError(f"m2dec_amd: scale_taps refused {S} -> {On} ({filter})")
+    return start, count, weights
+
+
+def frame_convert_host(f: Frame, fmt: str = "rgb", matrix: str = "bt709", full_range: bool = False, size=None,
+                       filter: str = "bilinear", dtype: str = "u8", mean=(0, 0, 0), std=(1, 1, 1)) -> bytes:
     """The output conversion (include/m2dec_amd.h) of a host frame on the CPU (m2dec_amd_frame_convert_host): the
-    cropped frame as NV12, interleaved RGB or planar RGB bytes.  Raises ValueError for an odd crop or size."""
+    cropped frame as NV12, interleaved RGB or planar RGB bytes; with ``size=(height, width)`` resampled by ``filter``
+    ("bilinear" / "area"), with ``dtype`` "f16" / "f32" stored as (q / 255 - mean) / std.  Raises ValueError for an
+    odd crop or size or a refused config."""
     L = lib()
-    cfg = _devout(fmt, matrix, full_range)
-    n = L.m2dec_amd_frame_out_bytes(cfg.format, f.width - f.crop[0] - f.crop[1], f.height - f.crop[2] - f.crop[3])
+    cfg = _devout(fmt, matrix, full_range, size, filter, dtype, mean, std)
+    n, _, _ = _out_bytes(cfg, f.width - f.crop[0] - f.crop[1], f.height - f.crop[2] - f.crop[3])
     out = ctypes.create_string_buffer(max(1, n))
-    if not n or L.m2dec_amd_frame_convert_host(ctypes.byref(f), ctypes.byref(cfg), out) < 0:
+    if L.m2dec_amd_frame_convert_host(ctypes.byref(f), ctypes.byref(cfg), out) < 0:
         raise ValueError("m2dec_amd: frame_convert_host refused the frame (odd or empty crop)")
     return out.raw[:n]
 
 
 def hip_frame_convert(luma: bytes, chroma: bytes, width: int, height: int, crop=(0, 0, 0, 0), fmt: str = "rgb",
-                      matrix: str = "bt709", full_range: bool = False, device: int = 0, out_offset: int = 0):
-    """Kernel parity entry (m2dec_amd_hip_frame_convert): k_frame_out over the uploaded planes, written
-    ``out_offset`` bytes into a device buffer.  Returns (frame bytes, the 64 guard bytes before, the 64 after)."""
+                      matrix: str = "bt709", full_range: bool = False, device: int = 0, out_offset: int = 0,
+                      size=None, filter: str = "bilinear", dtype: str = "u8", mean=(0, 0, 0), std=(1, 1, 1)):
+    """Kernel parity entry (m2dec_amd_hip_frame_convert): k_frame_out (k_frame_scale for ``size`` / a float
+    ``dtype``) over the uploaded planes, written ``out_offset`` bytes (a multiple of the element size) into a device
+    buffer.  Returns (frame bytes, the 64 guard bytes before, the 64 after)."""
     L = lib()
-    cfg = _devout(fmt, matrix, full_range)
-    n = L.m2dec_amd_frame_out_bytes(cfg.format, width - crop[0] - crop[1], height - crop[2] - crop[3])
+    cfg = _devout(fmt, matrix, full_range, size, filter, dtype, mean, std)
+    if size is None and dtype == "u8":  # (today's path: an odd crop is the library's to refuse)
+        n = L.m2dec_amd_frame_out_bytes(cfg.format, width - crop[0] - crop[1], height - crop[2] - crop[3])
+    else:
+        n, _, _ = _out_bytes(cfg, width - crop[0] - crop[1], height - crop[2] - crop[3])
+        if out_offset % _DTYPE_NUMPY[dtype][2]:
+            raise ValueError(f"m2dec_amd: out_offset {out_offset} is not a multiple of the {dtype} element size")
     out = ctypes.create_string_buffer(n + 128)
     cr = (ctypes.c_int16 * 4)(*crop)
     if len(luma) < width * height or len(chroma) < width * height // 2:
@@ -389,20 +461,21 @@ def hip_frame_convert(luma: bytes, chroma: bytes, width: int, height: int, crop=
 
 
 def frame_out_timing(reset: bool = False):
-    """(HIP-event microseconds, launches) of k_frame_out over the device decodes finished so far."""
+    """(HIP-event microseconds, launches) of k_frame_out / k_frame_scale over the device decodes finished so far."""
     us, n = ctypes.c_double(), ctypes.c_int64()
     lib().m2dec_amd_frame_out_timing(ctypes.byref(us), ctypes.byref(n), 1 if reset else 0)
     return us.value, n.value
 
 
 class DeviceFrames:
-    """The output frames of ``decode_to_device`` in device memory: ``n`` frames of ``shape[1:]`` bytes each, packed,
-    on ``device``.  ``numpy()`` copies them to the host; ``__cuda_array_interface__`` (version 3) hands the memory to
+    """The output frames of ``decode_to_device`` in device memory: ``n`` frames of ``shape[1:]`` elements of ``dtype``
+    ("u8" / "f16" / "f32") each, packed, on ``device``.  ``numpy()`` copies them to the host; ``__cuda_array_interface__`` (version 3) hands the memory to
     torch or cupy without a copy (``torch.as_tensor(frames, device="cuda:0")``) — the memory lives until ``close()``."""
 
-    def __init__(self, device: int, fmt: str):
+    def __init__(self, device: int, fmt: str, dtype: str = "u8"):
         self.device = device
         self.fmt = fmt
+        self.dtype = dtype
         self.ptr = None
         self.capacity = 0
         self.n = 0
@@ -418,13 +491,13 @@ class DeviceFrames:
     def __cuda_array_interface__(self):
         if not self.ptr:
             raise RuntimeError("m2dec_amd: DeviceFrames is empty or closed")
-        return {"shape": self.shape, "typestr": "|u1", "data": (int(self.ptr), False), "version": 3, "strides": None,
+        return {"shape": self.shape, "typestr": _DTYPE_NUMPY[self.dtype][1], "data": (int(self.ptr), False), "version": 3, "strides": None,
                 "stream": None}
 
     def numpy(self):
         import numpy as np
-        out = np.empty(self.shape, dtype=np.uint8)
-        if out.size and lib().m2dec_amd_device_read(self.device, self.ptr, out.ctypes.data, out.size) < 0:
+        out = np.empty(self.shape, dtype=np.dtype(_DTYPE_NUMPY[self.dtype][0]))
+        if out.size and lib().m2dec_amd_device_read(self.device, self.ptr, out.ctypes.data, out.nbytes) < 0:
             raise RuntimeError("m2dec_amd: device read failed")
         return out
 
@@ -451,16 +524,21 @@ class DeviceFrames:
 
 
 def decode_to_device(data: bytes, device: int = 0, fmt: str = "rgb", matrix: str = "bt709", full_range: bool = False,
-                     dpb: int = -1, stats: Optional[Stats] = None) -> DeviceFrames:
+                     dpb: int = -1, stats: Optional[Stats] = None, size=None, filter: str = "bilinear", dtype: str = "u8",
+                     mean=(0, 0, 0), std=(1, 1, 1)) -> DeviceFrames:
     """Decode an H.264 stream with the HIP back end and leave every output frame, cropped, in device memory
     (m2dec_amd_decode_stream_device): ``fmt`` "rgb" (N, H, W, 3), "rgbp" (N, 3, H, W) or "nv12" (N, H * 3 / 2, W),
     converted by k_frame_out with ``matrix`` "bt709" / "bt601" in limited or full range.  No pixel crosses to the
-    host (``stats.d2h_bytes`` stays 0).  One geometry per stream: a frame of another size ends the decode."""
+    host (``stats.d2h_bytes`` stays 0).  One geometry per stream: a frame of another size ends the decode.
+    ``size=(height, width)`` resamples every RGB frame on the device (k_frame_scale) with ``filter`` "bilinear"
+    (half-pixel centres, no antialias) or "area" (the exact box filter); ``dtype`` "f16" / "f32" stores
+    (q / 255 - mean) / std per channel instead of the uint8 q.  The frames then have the output size and dtype.
+    ValueError for a bad argument, before any GPU work."""
+    cfg = _devout(fmt, matrix, full_range, size, filter, dtype, mean, std)
     L = lib()
     if not L.m2dec_amd_hip_available():
         raise RuntimeError("m2dec_amd: no usable gfx950 device for the HIP back end")
-    cfg = _devout(fmt, matrix, full_range)
-    fr = DeviceFrames(device, fmt)
+    fr = DeviceFrames(device, fmt, dtype)
     cap = _max_frames(data)
 
     def _dst(_arg, index, width, height, nbytes):

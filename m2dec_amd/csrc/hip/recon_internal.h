@@ -103,9 +103,24 @@ static inline int picture_blocks_dp(int inter_workers, int row_wgs, int Hmb, boo
 
 /* frame_out.hip: enqueue k_frame_out on stream s — the picture at `pic` (the back end's layout: NV12, luma stride W,
  * chroma at + W * H; 4-byte aligned) cropped and converted as cfg says into dst (device memory, any alignment,
- * m2dec_amd_frame_out_bytes long).  -1 without a launch for a bad cfg, an odd crop or an empty cropped frame. */
+ * m2dec_amd_frame_out_bytes2 long).  An unscaled uint8 cfg goes to k_frame_out; anything else to k_frame_scale
+ * (dst then aligned to the element size), whose tap tables live in `tab`.  -1 without a launch for a bad cfg, an odd
+ * crop or an empty cropped frame. */
+struct m2r_fo_tables_t {
+	void *dev = nullptr;   /* device: per axis start[], count[] (int16) and weights[][32] (uint16) */
+	void *host = nullptr;  /* their host image (the upload is asynchronous: kept until release) */
+	int key[5] = {};       /* cw, ch, ow, oh, filter the tables were built for */
+	int pitch = 0, rows = 0, rows_log2 = 0; /* LDS geometry of k_frame_scale for them */
+	size_t off[6] = {};    /* byte offsets of xs, xc, xw, ys, yc, yw in dev */
+};
+/* the tables of cfg for this picture geometry into tab (nothing to do for an unscaled uint8 cfg or when tab holds
+ * them already): built on the host, uploaded on s; the only place that allocates.  0 / -1. */
+int m2r_frame_scale_tables(hipStream_t s, int W, int H, const int16_t crop[4], const m2dec_amd_devout_t *cfg,
+                           m2r_fo_tables_t *tab);
+/* frees tab's memory; the caller has waited for every kernel that reads it */
+void m2r_frame_scale_tables_release(m2r_fo_tables_t *tab);
 int m2r_frame_out_launch(hipStream_t s, const uint8_t *pic, int W, int H, const int16_t crop[4],
-                         const m2dec_amd_devout_t *cfg, uint8_t *dst);
+                         const m2dec_amd_devout_t *cfg, uint8_t *dst, m2r_fo_tables_t *tab);
 
 /* dynamic LDS bytes of one k_deblock workgroup for a W-sample-wide picture */
 size_t m2r_deblock_lds_bytes(int W, int Wmb);

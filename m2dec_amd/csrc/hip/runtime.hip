@@ -1286,6 +1286,7 @@ struct HipBackend {
 	int64_t fo_frames = 0;
 	std::mutex fo_mu;              /* fo_timed / fo_us / fo_frames: emit (API thread) and stage_drop (a pool worker) */
 	int *err_host = nullptr;       /* pinned: the kernels' error word as of finish */
+	m2r_fo_tables_t fo_tab;        /* k_frame_scale's tap tables: built at the first emit that needs them, kept */
 	/* guards Arena::held / pending / ext: records_busy reads them from any thread while the decoder's
 	 * serial calls (acquire, submit, flush, bind) change them */
 	std::mutex arena_mu;
@@ -1820,6 +1821,7 @@ void be_destroy(void *self)
 			g_pool.put_event(b->sc.dev, true, b->fo_ev[i][1]);
 		}
 		if (b->err_host) (void)hipHostFree(b->err_host);
+		m2r_frame_scale_tables_release(&b->fo_tab); /* (the copy stream was synchronised above) */
 		std::lock_guard<std::mutex> lk(g_fo_mu);
 		g_fo_us += b->fo_us;
 		g_fo_frames += b->fo_frames;
@@ -1974,9 +1976,11 @@ extern "C" int m2dec_amd_hip_backend_emit(const m2r_backend_t *be, int slot, con
 	CHECK(hipSetDevice(b->sc.dev));
 	if (b->fo_timed[slot] && hipEventQuery(b->fo_ev[slot][1]) == hipSuccess) fo_collect(b, slot);
 	CHECK(hipStreamWaitEvent(b->copy, b->slot_ev[slot], 0)); /* the picture's copy into the staging */
+	/* a scaled cfg's tables, outside the timed span: allocated and uploaded once per back end */
+	if (m2r_frame_scale_tables(b->copy, b->sc.W, b->sc.H, crop, cfg, &b->fo_tab) < 0) return -1;
 	const bool timed = b->timing && !b->fo_timed[slot];
 	if (timed) CHECK(hipEventRecord(b->fo_ev[slot][0], b->copy));
-	if (m2r_frame_out_launch(b->copy, b->stg[slot], b->sc.W, b->sc.H, crop, cfg, (uint8_t *)dst_dev) < 0) return -1;
+	if (m2r_frame_out_launch(b->copy, b->stg[slot], b->sc.W, b->sc.H, crop, cfg, (uint8_t *)dst_dev, &b->fo_tab) < 0) return -1;
 	if (timed) {
 		CHECK(hipEventRecord(b->fo_ev[slot][1], b->copy));
 		std::lock_guard<std::mutex> lk(b->fo_mu);

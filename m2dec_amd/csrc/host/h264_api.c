@@ -625,7 +625,8 @@ typedef struct {
  * device staging (complete at m2dec_amd_hip_backend_finish) */
 static void emit_device(driver_t *v, const m2d_frame_t *f)
 {
-	int slot = -1, cw, ch;
+	int slot = -1, cw, ch, ow = 0, oh = 0;
+	size_t bytes;
 	void *dst;
 	if (v->dv_failed) return;
 	for (int i = 0; i < v->nframes; ++i)
@@ -634,7 +635,12 @@ static void emit_device(driver_t *v, const m2d_frame_t *f)
 		v->dv_failed = 1;
 		return;
 	}
-	dst = v->dv->frame_dst(v->dv->arg, v->dv_index++, cw, ch, m2dec_amd_frame_out_bytes(v->dv->format, cw, ch));
+	bytes = m2dec_amd_frame_out_bytes2(v->dv, cw, ch, &ow, &oh); /* the output size: cropped, or the cfg's */
+	if (!bytes) {
+		v->dv_failed = 1;
+		return;
+	}
+	dst = v->dv->frame_dst(v->dv->arg, v->dv_index++, ow, oh, bytes);
 	if (!dst || m2dec_amd_hip_backend_emit(&v->d->backend, slot, f->crop, v->dv, dst) < 0) v->dv_failed = 1;
 }
 
@@ -798,7 +804,7 @@ int m2dec_amd_decode_stream_device(const uint8_t *data, size_t len, int device, 
                                    m2dec_amd_stats_t *stats)
 {
 	m2d_fo_coef_t k;
-	if (!data || !out || out->size < sizeof(*out) || !out->frame_dst || m2d_frame_out_coefs(out, &k) < 0) return -1;
+	if (!data || !out || out->size < offsetof(m2dec_amd_devout_t, arg) + sizeof(out->arg) /* (revision 6's struct) */ || !out->frame_dst || m2d_frame_out_coefs(out, &k) < 0) return -1;
 	return stream_core(data, len, NULL, device, dpb, -1, 0, NULL, NULL, NULL, NULL, out, stats);
 }
 

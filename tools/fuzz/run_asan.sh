@@ -10,7 +10,7 @@ gcc -O1 -g -fsanitize=address -fno-omit-frame-pointer -march=x86-64-v3 -std=gnu1
   $R/oracle/h265_oracle.c -lpthread -lm || exit 1
 # the output conversion's host restatement (frame_out.c) into exact-size buffers: every format, matrix, range and crop
 gcc -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer -std=gnu11 -I$R/include \
-  -I$R/m2dec_amd/csrc/host -o $T/frame_out $R/tools/fuzz/frame_out_asan.c $R/m2dec_amd/csrc/host/frame_out.c || exit 1
+  -I$R/m2dec_amd/csrc/host -o $T/frame_out $R/tools/fuzz/frame_out_asan.c $R/m2dec_amd/csrc/host/frame_out.c -lm || exit 1
 $T/frame_out || exit 1
 python3 - "$T" "$N" <<'PY'
 import os, sys, textwrap
